@@ -207,6 +207,18 @@ int sf_colsum_accum(const float* partial, int nb, int H, float* acc, int accumul
 int sf_rope(void* x, int dtype, long ld, int rows, int nheads, int hd, const void* cos_t, const void* sin_t,
             const long long* pos_ids, int pos_off, int max_pos, int backward, void* stream);
 
+/* ---- Ulysses sequence parallelism (attention_backend "usp", batch 1; llama3_eagle.py:1363-1505), ABI 6 additions.
+ * Send / receive layout [sp][chunk][w]: block j holds rank j's heads (q | k | v groups of nh/sp, nkv/sp heads) of this rank's tokens;
+ * received, it is the head-sharded [sp*chunk, w] operand of the attention kernels.
+ * pack_qkv forward : token rows [chunk, (nh+2nkv)*hd] -> send buffer, q / k rotated at pos_ids + pos_off (same bits as sf_rope
+ *                    followed by the permutation); backward: received d(q|k|v) [sp*chunk, w] -> token rows, transposed rotation.
+ * pack_o  : token rows [chunk, sp*w] -> [sp][chunk][w] (dO on the way to the heads); unpack_o: the inverse (O before o_proj). */
+int sf_ulysses_pack_qkv(const void* src, long ld_src, void* dst, long ld_dst, int chunk, int sp, int nh, int nkv, int hd,
+                        const void* cos_t, const void* sin_t, const long long* pos_ids, int pos_off, int max_pos, int backward,
+                        void* stream);
+int sf_ulysses_pack_o(const void* src, long ld_src, void* dst, long ld_dst, int chunk, int sp, int w, void* stream);
+int sf_ulysses_unpack_o(const void* src, long ld_src, void* dst, long ld_dst, int chunk, int sp, int w, void* stream);
+
 /* ---- SwiGLU on a fused [rows, 2I] gate|up buffer (llama3_eagle.py:1518-1549) --------------- */
 int sf_swiglu_fwd(const void* gu, int dtype, long ldgu, long rows, int I, void* act, long ldact, void* stream);
 int sf_swiglu_bwd(const void* dact, int dtype, long lddact, const void* gu, long ldgu, long rows, int I, void* dgu,

@@ -90,7 +90,10 @@ class OnlineEagle3Model(nn.Module):
 
     def __init__(self, draft_model: LlamaForCausalLMEagle3, length: int = 7, attention_backend: str = "hip",
                  lk_loss_type: Optional[str] = None, kl_scale: float = 1.0, kl_decay: float = 1.0,
-                 ploss_decay: float = 0.8):
+                 ploss_decay: float = 0.8, sp_group=None):
+        """``attention_backend="usp"``: Ulysses sequence parallelism over ``sp_group`` (set here, or later by
+        ``HipDPTrainingBackend.prepare_model`` / the strategy, before the first forward); every other value runs the one-rank
+        attention."""
         super().__init__()
         if lk_loss_type not in (None, "alpha", "lambda"):
             raise ValueError(f"Unknown lk loss type: {lk_loss_type}")  # core/lk_loss.py:99
@@ -99,6 +102,7 @@ class OnlineEagle3Model(nn.Module):
         self.draft_model = draft_model
         self.length = length
         self.attention_backend = attention_backend
+        self.sp_group = sp_group
         self.lk_loss_type, self.kl_scale, self.kl_decay = lk_loss_type, kl_scale, kl_decay
         self.ploss_decay = ploss_decay
         self._engine: Optional[Eagle3Engine] = None
@@ -111,8 +115,15 @@ class OnlineEagle3Model(nn.Module):
         constructing it (algorithms/model_providers.py:268-275); adopting the parameters into the flat buffer any
         earlier would be undone by that move."""
         if self._engine is None:
+            sp_group = None
+            if self.attention_backend == "usp":
+                if self.sp_group is None:
+                    raise ValueError("attention_backend 'usp' needs the SP process group (OnlineEagle3Model(sp_group=...), "
+                                     "ParallelConfig(sp_size=...) or Eagle3TrainStrategy(sp_group=...))")
+                sp_group = self.sp_group
             self._engine = Eagle3Engine(self.draft_model, ttt_length=self.length, ploss_decay=self.ploss_decay,
-                                        lk_loss_type=self.lk_loss_type, kl_scale=self.kl_scale, kl_decay=self.kl_decay)
+                                        lk_loss_type=self.lk_loss_type, kl_scale=self.kl_scale, kl_decay=self.kl_decay,
+                                        sp_group=sp_group)
             object.__setattr__(self.draft_model, "_hip_engine", self._engine)   # found by BF16Optimizer(draft_model)
         return self._engine
 
@@ -190,11 +201,15 @@ class Eagle3TrainStrategy:
 
     def __init__(self, eagle3_model: OnlineEagle3Model, *, target_head: Optional[TargetHead] = None,
                  ploss_decay: float = 0.8, compact_teacher: bool = True, compact_teacher_chunk_size: Optional[int] = None,
-                 pinned_staging: bool = True):
+                 pinned_staging: bool = True, sp_group=None):
         """``pinned_staging=False`` (A/B only, ``bench.py --feed cpu_batch_pageable``): CPU batches are shifted on the CPU and
         moved with the blocking pageable ``.to(device)`` the reference's strategy uses (strategies/base.py:256-284)."""
         self.pinned_staging = pinned_staging
         self.eagle3_model = eagle3_model
+        if sp_group is not None:        # attention_backend "usp": the SP group the engine exchanges over
+            if eagle3_model._engine is not None and eagle3_model._engine.sp_group is not sp_group:
+                raise ValueError("sp_group must be set before the HIP engine is built (the first forward)")
+            eagle3_model.sp_group = sp_group
         self.target_head = target_head
         self.ploss_decay = ploss_decay
         self._stager = None

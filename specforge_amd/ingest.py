@@ -52,6 +52,28 @@ def normalize_offline_sample(raw: Dict[str, torch.Tensor], max_len: int) -> Dict
                 hidden_state=hidden_state, input_ids=input_ids)
 
 
+def usp_shard(sample: Dict[str, torch.Tensor], *, ttt_length: int, sp_rank: int, sp_size: int) -> Dict[str, torch.Tensor]:
+    """One sample's shard for Ulysses rank ``sp_rank`` of ``sp_size`` (data/preprocessing.py:446-521, ``process_data_usp``) from a
+    normalised batch-1 sample (``normalize_offline_sample``: the global last loss-mask position is already zero): chunk =
+    ceil(S / sp) rows from sp_rank * chunk plus ``ttt_length`` rows of overlap from the next shard, zero-padded past the sample's
+    end; attention_mask marks the real rows, position_ids the chunk's global positions."""
+    S = sample["input_ids"].shape[1]
+    chunk = (S + sp_size - 1) // sp_size
+    start, local = sp_rank * chunk, chunk + ttt_length
+    end = min(start + local, S)
+    out = {}
+    for k in ("hidden_state", "target", "input_ids", "loss_mask"):
+        t = sample[k][:, start:end]
+        pad = local - t.shape[1]
+        out[k] = torch.cat([t, t.new_zeros((t.shape[0], pad) + tuple(t.shape[2:]))], dim=1) if pad > 0 else t.contiguous()
+    valid = max(end - start, 0)
+    dev = sample["input_ids"].device
+    out["attention_mask"] = torch.zeros(1, local, dtype=torch.long, device=dev)
+    out["attention_mask"][:, :valid] = 1
+    out["position_ids"] = torch.arange(start, start + chunk, dtype=torch.long, device=dev).unsqueeze(0)
+    return out
+
+
 # ---- direct reader ---------------------------------------------------------------------------------------------------
 # ``torch.save`` writes an uncompressed zip: ``<name>/data.pkl`` (a pickle whose tensors are persistent-id references) and one
 # 64-byte-aligned record ``<name>/data/<key>`` per storage.  For the ingest that is all that is needed: the byte range of every
@@ -162,8 +184,15 @@ _LAYOUT_CACHE_MAX = 1 << 16     # entries; a multi-million-file dataset must not
 class HiddenStateIngest:
     def __init__(self, files: Sequence[str], *, batch_size: int, max_len: int, target_hidden_size: Optional[int] = None, device="cuda",
                  dp_rank: int = 0, dp_size: int = 1, seed: int = 0, shuffle: bool = True, pad_multiple: int = 1,
-                 slots: int = 2, reader_threads: int = 4, direct: bool = True):
-        """``target_hidden_size=None``: taken from the first file read (the reference's loader does not know it either)."""
+                 slots: int = 2, reader_threads: int = 4, direct: bool = True, sp_rank: int = 0, sp_size: int = 1, ttt_length: int = 7):
+        """``target_hidden_size=None``: taken from the first file read (the reference's loader does not know it either).
+        ``sp_size > 1`` (attention_backend "usp"): every batch is this SP rank's shard of one sample (``usp_shard``); ``dp_rank`` /
+        ``dp_size`` are then the DRAFT-DP rank and size, so the sp peers of a group read the same sample (launch.py:177-205)."""
+        if sp_size > 1 and batch_size != 1:
+            raise ValueError("batch_size must be 1 with attention_backend 'usp'")
+        if not 0 <= sp_rank < sp_size:
+            raise ValueError(f"sp_rank {sp_rank} outside 0..{sp_size - 1}")
+        self.sp_rank, self.sp_size, self.ttt_length = sp_rank, sp_size, ttt_length
         self.files = list(files)
         self.B, self.max_len, self.Ht = batch_size, max_len, target_hidden_size
         self.device = torch.device(device)
@@ -370,7 +399,11 @@ class HiddenStateIngest:
                 else:
                     tensors = {k: v[:nb, :L].clone() for k, v in slot.h.items()}
                 prev = si
-                yield TrainBatch(tensors, {"target_repr": "hidden_state", "sample_files": list(g), "loss_mask_suffix_counts": counts})
+                md = {"target_repr": "hidden_state", "sample_files": list(g), "loss_mask_suffix_counts": counts}
+                if self.sp_size > 1:        # (the engine's USP mode runs the dense lm_head: no suffix counts for the shard)
+                    tensors = usp_shard(tensors, ttt_length=self.ttt_length, sp_rank=self.sp_rank, sp_size=self.sp_size)
+                    del md["loss_mask_suffix_counts"]
+                yield TrainBatch(tensors, md)
         finally:
             # the consumer may abandon the iterator mid-epoch (max_steps reached): release the loader thread
             stop.set()

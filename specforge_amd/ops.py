@@ -288,6 +288,40 @@ def rope_(x: torch.Tensor, nheads: int, hd: int, cos_t: torch.Tensor, sin_t: tor
     return x
 
 
+def ulysses_pack_qkv(src: torch.Tensor, dst: torch.Tensor, *, sp: int, nh: int, nkv: int, hd: int, cos_t: torch.Tensor,
+                     sin_t: torch.Tensor, pos_ids: torch.Tensor, pos_off: int, backward: bool = False):
+    """Ulysses exchange image of one TTT step's q | k | v (batch 1).  forward: token rows src [chunk, (nh+2nkv)*hd] -> dst
+    [sp*chunk, (nh+2nkv)*hd/sp] (block j = rank j's heads), q / k rotated at pos_ids + pos_off.  backward: the received
+    head-sharded gradient src [sp*chunk, w] -> token rows dst [chunk, (nh+2nkv)*hd], transposed rotation."""
+    L = _lib.lib()
+    assert src.dtype == dst.dtype == cos_t.dtype == torch.bfloat16 and cos_t.is_contiguous() and sin_t.is_contiguous()
+    assert pos_ids.dtype == torch.int64
+    tok, sh = (dst, src) if backward else (src, dst)
+    chunk = tok.shape[0]
+    assert sh.shape == (sp * chunk, (nh + 2 * nkv) * hd // sp) and tok.shape[1] >= (nh + 2 * nkv) * hd and pos_ids.numel() >= chunk
+    _lib.check(L.sf_ulysses_pack_qkv(_p(src), _rowmajor(src), _p(dst), _rowmajor(dst), chunk, sp, nh, nkv, hd, _p(cos_t), _p(sin_t),
+                                     _p(pos_ids), pos_off, cos_t.shape[0], 1 if backward else 0, _stream()), "sf_ulysses_pack_qkv")
+    return dst
+
+
+def ulysses_pack_o(src: torch.Tensor, dst: torch.Tensor, *, sp: int):
+    """token rows src [chunk, sp*w] -> dst [sp*chunk, w] (block j = columns j*w .. (j+1)*w)"""
+    L = _lib.lib()
+    chunk, w = src.shape[0], dst.shape[1]
+    assert src.dtype == dst.dtype == torch.bfloat16 and dst.shape[0] == sp * chunk and src.shape[1] >= sp * w
+    _lib.check(L.sf_ulysses_pack_o(_p(src), _rowmajor(src), _p(dst), _rowmajor(dst), chunk, sp, w, _stream()), "sf_ulysses_pack_o")
+    return dst
+
+
+def ulysses_unpack_o(src: torch.Tensor, dst: torch.Tensor, *, sp: int):
+    """inverse of ulysses_pack_o: src [sp*chunk, w] -> token rows dst [chunk, sp*w]"""
+    L = _lib.lib()
+    chunk, w = dst.shape[0], src.shape[1]
+    assert src.dtype == dst.dtype == torch.bfloat16 and src.shape[0] == sp * chunk and dst.shape[1] >= sp * w
+    _lib.check(L.sf_ulysses_unpack_o(_p(src), _rowmajor(src), _p(dst), _rowmajor(dst), chunk, sp, w, _stream()), "sf_ulysses_unpack_o")
+    return dst
+
+
 def swiglu_fwd(gu: torch.Tensor, act: torch.Tensor):
     L = _lib.lib()
     rows, I = act.shape

@@ -81,6 +81,30 @@ class HipEagle3TrainStrategy(Eagle3TrainStrategy):
     name = ALGORITHM_NAME   # the checkpoint's ``strategy`` field must equal the algorithm name (training/trainer.py:288)
 
 
+def check_training_topology(t, draft_config=None) -> None:
+    """Refuse, before any step, the training topologies the HIP path does not implement (config/schema.py:523-531,590-604): they
+    would otherwise train each rank's shard as if it were a whole sample.  Ulysses SP runs on ``Eagle3Engine``'s USP mode through the
+    Python API (``HipDPTrainingBackend(ParallelConfig(sp_size=N))`` + ``HiddenStateIngest(sp_rank=, sp_size=)``); this plugin does
+    not wire its loader and groups, so ``attention_backend: usp`` is refused here too -- after the checks that name a specific key."""
+    if int(getattr(t, "sp_ring_size", 1) or 1) > 1:
+        raise ValueError(f"training.sp_ring_size = {t.sp_ring_size}: ring attention is not implemented by the HIP path "
+                         "(use sp_ulysses_size alone)")
+    if int(getattr(t, "tp_size", 1) or 1) > 1:
+        raise ValueError(f"training.tp_size = {t.tp_size}: tensor parallelism is not implemented by the HIP path")
+    if getattr(t, "attention_backend", None) != "usp":
+        return
+    if int(getattr(t, "batch_size", 1) or 1) != 1:
+        raise ValueError("training.batch_size must be 1 with attention_backend 'usp'")
+    sp = int(getattr(t, "sp_ulysses_size", 1) or 1)
+    if draft_config is not None:
+        c = draft_config if isinstance(draft_config, DraftConfig) else DraftConfig.from_hf(draft_config)
+        if c.num_attention_heads % sp or c.num_key_value_heads % sp:
+            raise ValueError(f"training.sp_ulysses_size {sp} must divide num_attention_heads ({c.num_attention_heads}) and "
+                             f"num_key_value_heads ({c.num_key_value_heads})")
+    raise ValueError("training.attention_backend 'usp': the plugin's loader does not shard samples over the SP ranks; drive USP through "
+                     "the Python API (HipDPTrainingBackend(ParallelConfig(sp_size=...)), HiddenStateIngest(sp_rank=..., sp_size=...))")
+
+
 def _training_model_factory():
     import specforge.algorithms.model_providers as mp
 
@@ -89,6 +113,7 @@ def _training_model_factory():
     def build(config, draft_model, draft_config, target_config, _tokenizer):
         """``build_eagle3_model`` (algorithms/model_providers.py:255-291) with the HIP composite"""
         t = config.training
+        check_training_topology(t, draft_config)
         model = OnlineEagle3Model(draft_model=draft_model, length=t.ttt_length, attention_backend=t.attention_backend,
                                   lk_loss_type=t.lk_loss_type, kl_scale=t.kl_scale, kl_decay=t.kl_decay)
         model = model.to(device=mp._device(), dtype=mp._torch_dtype(config))

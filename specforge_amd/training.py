@@ -193,6 +193,24 @@ class ParallelConfig:
     fsdp_process_group: Any = None
 
 
+def make_sp_groups(sp_size: int):
+    """(sp_group, draft_dp_group) of this rank on the mesh ("draft_dp", "sp") of the reference (distributed.py:134-195): the sp
+    peers are consecutive ranks, the draft-dp group takes one rank of each.  Every rank creates every group, in the same order."""
+    world, rank = dist.get_world_size(), dist.get_rank()
+    if sp_size < 1 or world % sp_size:
+        raise ValueError(f"sp_ulysses_size {sp_size} must divide the world size {world}")
+    sp_group = dp_group = None
+    for i in range(world // sp_size):
+        g = dist.new_group(list(range(i * sp_size, (i + 1) * sp_size)))
+        if rank // sp_size == i:
+            sp_group = g
+    for j in range(sp_size):
+        g = dist.new_group(list(range(j, world, sp_size)))
+        if rank % sp_size == j:
+            dp_group = g
+    return sp_group, dp_group
+
+
 class HipDPTrainingBackend:
     name = "hip_dp"
 
@@ -214,6 +232,14 @@ class HipDPTrainingBackend:
         self._pending_single = False
         self._sync_this_backward = True
         self.no_sync_backwards = 0  # telemetry: micro-steps that skipped the collective
+        # Ulysses SP (attention_backend "usp"): the SP and draft-dp groups of the reference's mesh.  Gradients stay averaged over the
+        # whole group above (training/backend.py:121): the sp ranks of one sample each hold the gradient of their shard's loss.
+        self.sp_size = int(self.parallel_config.sp_size)
+        if self.parallel_config.tp_size > 1:
+            raise ValueError(f"tp_size {self.parallel_config.tp_size}: tensor parallelism is not implemented by the HIP path")
+        self.sp_group = self.draft_dp_group = None
+        if self.sp_size > 1:
+            self.sp_group, self.draft_dp_group = make_sp_groups(self.sp_size)
 
     @property
     def optimizer_state_is_replicated(self) -> bool:
@@ -221,6 +247,15 @@ class HipDPTrainingBackend:
 
     def prepare_model(self, model: OnlineEagle3Model, *, wrap: bool = True, optimizer_target=None) -> nn.Module:
         self.module = model
+        if self.sp_size > 1:
+            if model.attention_backend != "usp":
+                raise ValueError(f"sp_size {self.sp_size} needs attention_backend 'usp' (got {model.attention_backend!r})")
+            if model.sp_group is not None and model.sp_group is not self.sp_group:
+                raise ValueError("the model already has another SP group than the one this backend built for sp_size "
+                                 f"{self.sp_size}; set one of them only")
+            if model._engine is not None and model._engine.sp_group is not self.sp_group:
+                raise ValueError("sp_size must be set before the HIP engine is built (the first forward)")
+            model.sp_group = self.sp_group
         use_dp = self.world > 1 or (self._force_collectives and dist.is_available() and dist.is_initialized())
         model.engine.on_bucket_ready = self._bucket_ready if use_dp else None
         if use_dp:  # replicas must start identical (DDP broadcasts rank 0's parameters)
