@@ -313,6 +313,25 @@ int sf_attn_bwd_dkv(const void* q, long ldq, const void* dout, long lddo, const 
                     const float* delta, float* dk, float* dv, long lddk, int B, int S, int nh, int nkv, int hd,
                     float scale, float* workspace, long workspace_floats, void* stream);
 
+/* Query offset (ABI 6, ring sequence parallelism): the same kernels for a shard of Sq queries at the global positions
+ * [q_off, q_off + Sq) of a longer sequence.  q / o / dout / dq / lse / delta hold the Sq local rows per batch ([B*Sq, ...],
+ * [B, nh, Sq]); k0 / v0 and the fp32 dk / dv hold the q_off + Sq global key rows [0, q_off + Sq) per batch.  Local query t sees
+ * keys 0 .. q_off + t, and the diagonal branches kd / vd ([B*Sq, nkv*hd]) at its own row.  kv_len counts global keys (a device
+ * array: values above q_off + Sq act as q_off + Sq).  q_off >= 0, any value; q_off = 0 gives the entry points above bit for bit.
+ * dk / dv (+=) receive this shard's share of every key's gradient -- keys past q_off + Sq - 1 have none; the sum over the shards of
+ * a sequence is the unsharded gradient.  The key buffer (fwd, dQ) and q / dout (dK/dV) must fit a 2 GiB buffer descriptor. */
+int sf_attn_fwd_off(const void* q, long ldq, const void* k0, long ldk, const void* v0, const void* const* kd,
+                    const void* const* vd, int ndiag, const int* kv_len, void* o, long ldo, float* lse, int B, int Sq,
+                    int q_off, int nh, int nkv, int hd, float scale, void* stream);
+int sf_attn_bwd_dq_off(const void* q, long ldq, const void* dout, long lddo, const void* k0, long ldk, const void* v0,
+                       long ldv, const int* kv_len, const float* lse, const float* delta,
+                       const float* dq_init, void* dq, long lddq, int B, int Sq, int q_off, int nh, int nkv, int hd, float scale,
+                       void* stream);
+long sf_attn_bwd_dkv_off_workspace_floats(int B, int Sq, int q_off, int nh, int nkv, int hd);
+int sf_attn_bwd_dkv_off(const void* q, long ldq, const void* dout, long lddo, const void* k0, long ldk, const void* v0, long ldv,
+                        const int* kv_len, const float* lse, const float* delta, float* dk, float* dv, long lddk, int B, int Sq,
+                        int q_off, int nh, int nkv, int hd, float scale, float* workspace, long workspace_floats, void* stream);
+
 /* ---- optimizer: BF16Optimizer.step on flat buffers (specforge/optimizer.py:95-168) ---------
  * norm_out[0] = prescale*sqrt(sum float(g)^2); adamw: clip = min(1, max_norm/(norm+1e-6))
  * (max_norm <= 0 disables), g32 = float(g)*clip*grad_prescale, torch.optim.AdamW update of the

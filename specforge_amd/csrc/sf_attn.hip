@@ -59,14 +59,14 @@ SF_GLOBAL void SF_LAUNCH_BOUNDS(NW * 64, AttnOcc<HD>::kWgPerCu) attn_fwd_kernel(
         g = h / (p.nh / p.nkv);
     }
     const int qb0 = qbi * QB;
-    const int S = p.S;
-    const int kvlen = p.kv_len ? p.kv_len[b] : S;
-    const int qw0 = qb0 + wave * 32;
+    const int S = p.S, qo = p.q_off, SK = qo + S;   // local queries; keys [0, SK) (ring shard: q_off > 0)
+    const int kvlen = p.kv_len ? p.kv_len[b] : SK;
+    const int qw0 = qb0 + wave * 32, qg0 = qo + qw0;   // first query of this wave: local row, global position
     const int qi = qw0 + c;                       // this lane's query position
     const bool qok = qi < S;
     const long qrow = (long)b * S + (qok ? qi : S - 1);
     const float sc = p.scale * kLog2e;
-    const int lim = qi < kvlen - 1 ? qi : kvlen - 1;   // last key this query attends to in block 0
+    const int lim = qo + qi < kvlen - 1 ? qo + qi : kvlen - 1;   // last key this query attends to in block 0
     FragOff<HD> fo;
     fo.init(lane);
 
@@ -82,12 +82,12 @@ SF_GLOBAL void SF_LAUNCH_BOUNDS(NW * 64, AttnOcc<HD>::kWgPerCu) attn_fwd_kernel(
         for (int r = 0; r < 16; ++r) acc_o[d][r] = 0.f;
     float m = kNegBig, lpart = 0.f;
 
-    const SfBufB kbuf = rows_buf<HD>(p.k0 + (long)b * S * p.ldk + g * HD, p.ldk, S);
-    const SfBufB vbuf = rows_buf<HD>(p.v0 + (long)b * S * p.ldk + g * HD, p.ldk, S);
+    const SfBufB kbuf = rows_buf<HD>(p.k0 + (long)b * SK * p.ldk + g * HD, p.ldk, SK);
+    const SfBufB vbuf = rows_buf<HD>(p.v0 + (long)b * SK * p.ldk + g * HD, p.ldk, SK);
     const unsigned tile_bytes = (unsigned)(64 * p.ldk * 2);
     TileStage<HD, 64, NW> st;
     st.init(p.ldk, wave, lane);
-    int kend = qb0 + QB < S ? qb0 + QB : S;  // causal upper bound for this block
+    int kend = qo + (qb0 + QB < S ? qb0 + QB : S);  // causal upper bound for this block
     if (kvlen < kend) kend = kvlen;
     const int ntiles = (kend + 63) / 64;
     if (ntiles > 0) {
@@ -107,9 +107,9 @@ SF_GLOBAL void SF_LAUNCH_BOUNDS(NW * 64, AttnOcc<HD>::kWgPerCu) attn_fwd_kernel(
         }
         const char* lds_k = smem + (kt & 1) * TILE;
         const char* lds_v = lds_k + 64 * HD * 2;
-        if (key0 > qw0 + 31) continue;  // whole tile above this wave's diagonal (wave-uniform)
+        if (key0 > qg0 + 31) continue;  // whole tile above this wave's diagonal (wave-uniform)
         if (SF_ATTN_DBG(p, 2)) continue;
-        const bool need_mask = (key0 + 63 > qw0) || (key0 + 63 >= kvlen);
+        const bool need_mask = (key0 + 63 > qg0) || (key0 + 63 >= kvlen);
         sf_v16f s[2];
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb)
@@ -635,14 +635,14 @@ SF_GLOBAL void SF_LAUNCH_BOUNDS(NW * 64, AttnOcc<HD>::kWgPerCu) attn_bwd_dq_kern
         g = h / (p.nh / p.nkv);
     }
     const int qb0 = qbi * QB;
-    const int S = p.S;
-    const int kvlen = p.kv_len ? p.kv_len[b] : S;
-    const int qw0 = qb0 + wave * 32;
+    const int S = p.S, qo = p.q_off, SK = qo + S;   // local queries; keys [0, SK) (ring shard: q_off > 0)
+    const int kvlen = p.kv_len ? p.kv_len[b] : SK;
+    const int qw0 = qb0 + wave * 32, qg0 = qo + qw0;   // first query of this wave: local row, global position
     const int qi = qw0 + c;
     const bool qok = qi < S;
     const long qrow = (long)b * S + (qok ? qi : S - 1);
     const float sc = p.scale * kLog2e;
-    const int lim = qi < kvlen - 1 ? qi : kvlen - 1;
+    const int lim = qo + qi < kvlen - 1 ? qo + qi : kvlen - 1;
     FragOff<HD> fo;
     fo.init(lane);
     const long li = ((long)b * p.nh + h) * S + (qok ? qi : S - 1);
@@ -661,13 +661,13 @@ SF_GLOBAL void SF_LAUNCH_BOUNDS(NW * 64, AttnOcc<HD>::kWgPerCu) attn_bwd_dq_kern
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[d][r] = 0.f;
 
-    const SfBufB kbuf = rows_buf<HD>(p.k0 + (long)b * S * p.ldk + g * HD, p.ldk, S);
-    const SfBufB vbuf = rows_buf<HD>(p.v0 + (long)b * S * p.ldv + g * HD, p.ldv, S);
+    const SfBufB kbuf = rows_buf<HD>(p.k0 + (long)b * SK * p.ldk + g * HD, p.ldk, SK);
+    const SfBufB vbuf = rows_buf<HD>(p.v0 + (long)b * SK * p.ldv + g * HD, p.ldv, SK);
     const unsigned ktile = (unsigned)(64 * p.ldk * 2), vtile = (unsigned)(64 * p.ldv * 2);
     TileStage<HD, 64, NW> stk, stv;
     stk.init(p.ldk, wave, lane);
     stv.init(p.ldv, wave, lane);
-    int kend = qb0 + QB < S ? qb0 + QB : S;
+    int kend = qo + (qb0 + QB < S ? qb0 + QB : S);
     if (kvlen < kend) kend = kvlen;
     const int ntiles = (kend + 63) / 64;
     if (ntiles > 0) {
@@ -690,7 +690,7 @@ SF_GLOBAL void SF_LAUNCH_BOUNDS(NW * 64, AttnOcc<HD>::kWgPerCu) attn_bwd_dq_kern
         }
         const char* lds_k = smem + (kt & 1) * TILE;
         const char* lds_v = lds_k + 64 * HD * 2;
-        if (key0 > qw0 + 31) continue;
+        if (key0 > qg0 + 31) continue;
         sf_v16f s[2], dp[2];
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb)
@@ -703,7 +703,7 @@ SF_GLOBAL void SF_LAUNCH_BOUNDS(NW * 64, AttnOcc<HD>::kWgPerCu) attn_bwd_dq_kern
                 s[kb] = sf_mfma32(frag_rows<HD>(lds_k, kb * 32, ks, fo), qf[ks], s[kb]);
                 dp[kb] = sf_mfma32(frag_rows<HD>(lds_v, kb * 32, ks, fo), dof[ks], dp[kb]);
             }
-        const bool need_mask = (key0 + 63 > qw0) || (key0 + 63 >= kvlen);  // wave-uniform
+        const bool need_mask = (key0 + 63 > qg0) || (key0 + 63 >= kvlen);  // wave-uniform
         if (need_mask) {
             const int rel = lim - key0 - 4 * hi;
             mask_scores(s[0], rel);          // exp2(-inf) == 0: masked keys carry no probability, hence no dS
@@ -753,9 +753,10 @@ SF_GLOBAL void SF_LAUNCH_BOUNDS(NW * 64, AttnOcc<HD>::kWgPerCu) attn_bwd_dq_kern
 
 constexpr int kAttnFwdWaves = 4;
 
-extern "C" int sf_attn_fwd(const void* q, long ldq, const void* k0, long ldk, const void* v0, const void* const* kd,
-                           const void* const* vd, int ndiag, const int* kv_len, void* o, long ldo, float* lse, int B,
-                           int S, int nh, int nkv, int hd, float scale, void* stream) {
+// S = local queries; the key buffers hold q_off + S rows per batch (sf_attn_common.h: query offset)
+static int attn_fwd_entry(const void* q, long ldq, const void* k0, long ldk, const void* v0, const void* const* kd,
+                          const void* const* vd, int ndiag, const int* kv_len, void* o, long ldo, float* lse, int B,
+                          int S, int q_off, int nh, int nkv, int hd, float scale, void* stream) {
     SF_CHECK_ARG(B > 0 && S > 0 && nh > 0 && nkv > 0 && nh % nkv == 0, "sf_attn_fwd: bad shape");
     SF_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldo % 8 == 0, "sf_attn_fwd: row strides must be multiples of 8 (16-byte segments)");
     SF_CHECK_ARG(ndiag >= 0 && ndiag <= kMaxDiag, "sf_attn_fwd: at most 32 diagonal branches");
@@ -767,15 +768,15 @@ extern "C" int sf_attn_fwd(const void* q, long ldq, const void* k0, long ldk, co
     for (int i = 0; i < ndiag; ++i) { p.kd[i] = (const sf_bf16*)kd[i]; p.vd[i] = (const sf_bf16*)vd[i]; }
     p.ndiag = ndiag; p.kv_len = kv_len;
     p.o = (sf_bf16*)o; p.ldo = ldo; p.lse = lse;
-    p.B = B; p.S = S; p.nh = nh; p.nkv = nkv; p.scale = scale;
+    p.B = B; p.S = S; p.nh = nh; p.nkv = nkv; p.scale = scale; p.q_off = q_off;
     p.dbg = sf_knob("SF_ATTN_DBG", 0);
     p.l2_map = sf_knob("SF_ATTN_L2MAP", 1);
-    SF_CHECK_ARG((long)S * ldk * 2 < (1L << 31), "sf_attn_fwd: S * ldk exceeds the 2 GiB range of a buffer descriptor");
+    SF_CHECK_ARG(((long)q_off + S) * ldk * 2 < (1L << 31), "sf_attn_fwd: S * ldk exceeds the 2 GiB range of a buffer descriptor");
     constexpr int NW = kAttnFwdWaves;
     const long nqb = (S + NW * 32 - 1) / (NW * 32);
     dim3 grid(p.l2_map ? attn_pair_major_grid(nqb * (nh / nkv), (long)nkv * B) : (unsigned)(nqb * nh * B));
 #if defined(SF_ABLATE) && !defined(SF_EMU)
-    if (sf_knob("SF_ATTN_FWD_W4", 0))   // tools build: the measured-and-rejected one-wave-per-SIMD variant
+    if (q_off == 0 && sf_knob("SF_ATTN_FWD_W4", 0))   // tools build: the measured-and-rejected one-wave-per-SIMD variant
         return sfattn_w4::attn_fwd(q, ldq, k0, ldk, v0, kd, vd, ndiag, kv_len, o, ldo, lse, B, S, nh, nkv, hd, scale, stream);
 #endif
     // head_dim 256: one wave per SIMD, slot-planned (sf_attn_w1.hip); the generic instantiation stays as the tools build's A/B
@@ -783,6 +784,19 @@ extern "C" int sf_attn_fwd(const void* q, long ldq, const void* k0, long ldk, co
     SF_HD_DISPATCH(hd, SF_ALLOW_SMEM((attn_fwd_kernel<HD, NW>), 2 * 128 * HD * 2);
                    SF_LAUNCH((attn_fwd_kernel<HD, NW>), grid, dim3(NW * 64), 2 * 128 * HD * 2, stream, p));
     return sf_check_launch("sf_attn_fwd");
+}
+
+extern "C" int sf_attn_fwd(const void* q, long ldq, const void* k0, long ldk, const void* v0, const void* const* kd,
+                           const void* const* vd, int ndiag, const int* kv_len, void* o, long ldo, float* lse, int B,
+                           int S, int nh, int nkv, int hd, float scale, void* stream) {
+    return attn_fwd_entry(q, ldq, k0, ldk, v0, kd, vd, ndiag, kv_len, o, ldo, lse, B, S, 0, nh, nkv, hd, scale, stream);
+}
+
+extern "C" int sf_attn_fwd_off(const void* q, long ldq, const void* k0, long ldk, const void* v0, const void* const* kd,
+                               const void* const* vd, int ndiag, const int* kv_len, void* o, long ldo, float* lse, int B,
+                               int Sq, int q_off, int nh, int nkv, int hd, float scale, void* stream) {
+    SF_CHECK_ARG(q_off >= 0 && (long)q_off + Sq <= 0x3fffffffL, "sf_attn_fwd_off: q_off must be >= 0 (and q_off + Sq < 2^30)");
+    return attn_fwd_entry(q, ldq, k0, ldk, v0, kd, vd, ndiag, kv_len, o, ldo, lse, B, Sq, q_off, nh, nkv, hd, scale, stream);
 }
 
 extern "C" int sf_attn_bwd_pre(const void* q, long ldq, const void* o, long ldo, const void* dout, long lddo,
@@ -871,7 +885,7 @@ extern "C" int sf_attn_bwd_diag(const void* q, long ldq, const void* o, long ldo
 static int fill_bwd_args(AttnBwdArgs& p, const void* q, long ldq, const void* dout, long lddo,
                          const void* k0, long ldk, const void* v0, long ldv,
                          const int* kv_len, const float* lse, const float* delta, const float* dq_init, void* dq,
-                         long lddq, float* dk, float* dv, long lddk, int B, int S, int nh, int nkv, float scale) {
+                         long lddq, float* dk, float* dv, long lddk, int B, int S, int nh, int nkv, float scale, int q_off = 0) {
     memset(&p, 0, sizeof(p));
     p.q = (const sf_bf16*)q; p.ldq = ldq;
     p.dout = (const sf_bf16*)dout; p.lddo = lddo;
@@ -880,27 +894,27 @@ static int fill_bwd_args(AttnBwdArgs& p, const void* q, long ldq, const void* do
     p.kv_len = kv_len; p.lse = lse; p.delta = delta; p.dq_init = dq_init;
     p.dq = (sf_bf16*)dq; p.lddq = lddq;
     p.dk = dk; p.dv = dv; p.lddk = lddk;
-    p.B = B; p.S = S; p.nh = nh; p.nkv = nkv; p.scale = scale;
+    p.B = B; p.S = S; p.nh = nh; p.nkv = nkv; p.scale = scale; p.q_off = q_off;
     p.l2_map = sf_knob("SF_ATTN_L2MAP", 1);
     return 0;
 }
 
-extern "C" int sf_attn_bwd_dq(const void* q, long ldq, const void* dout, long lddo, const void* k0, long ldk,
-                              const void* v0, long ldv, const int* kv_len, const float* lse,
-                              const float* delta, const float* dq_init, void* dq, long lddq, int B, int S, int nh,
-                              int nkv, int hd, float scale, void* stream) {
+static int attn_bwd_dq_entry(const void* q, long ldq, const void* dout, long lddo, const void* k0, long ldk,
+                             const void* v0, long ldv, const int* kv_len, const float* lse,
+                             const float* delta, const float* dq_init, void* dq, long lddq, int B, int S, int q_off, int nh,
+                             int nkv, int hd, float scale, void* stream) {
     SF_CHECK_ARG(B > 0 && S > 0 && nh > 0 && nkv > 0 && nh % nkv == 0, "sf_attn_bwd_dq: bad shape");
     SF_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && lddo % 8 == 0 && lddq % 8 == 0,
                  "sf_attn_bwd_dq: row strides must be multiples of 8 (16-byte segments)");
 #if defined(SF_ABLATE) && !defined(SF_EMU)
-    if (sf_knob("SF_ATTN_DQ_W4", 0))    // tools build: the measured-and-rejected one-wave-per-SIMD variant
+    if (q_off == 0 && sf_knob("SF_ATTN_DQ_W4", 0))    // tools build: the measured-and-rejected one-wave-per-SIMD variant
         return sfattn_w4::attn_bwd_dq(q, ldq, dout, lddo, k0, ldk, v0, ldv, kv_len, lse, delta, dq_init, dq, lddq, B, S, nh, nkv, hd,
                                       scale, stream);
 #endif
     AttnBwdArgs p;
     fill_bwd_args(p, q, ldq, dout, lddo, k0, ldk, v0, ldv, kv_len, lse, delta, dq_init, dq, lddq,
-                  nullptr, nullptr, 0, B, S, nh, nkv, scale);
-    SF_CHECK_ARG((long)S * ldk * 2 < (1L << 31) && (long)S * ldv * 2 < (1L << 31),
+                  nullptr, nullptr, 0, B, S, nh, nkv, scale, q_off);
+    SF_CHECK_ARG(((long)q_off + S) * ldk * 2 < (1L << 31) && ((long)q_off + S) * ldv * 2 < (1L << 31),
                  "sf_attn_bwd_dq: S * ld exceeds the 2 GiB range of a buffer descriptor");
     constexpr int NW = kAttnFwdWaves;
     const long nqb = (S + NW * 32 - 1) / (NW * 32);
@@ -909,4 +923,21 @@ extern "C" int sf_attn_bwd_dq(const void* q, long ldq, const void* dout, long ld
     SF_HD_DISPATCH(hd, SF_ALLOW_SMEM((attn_bwd_dq_kernel<HD, NW>), 2 * 128 * HD * 2);
                    SF_LAUNCH((attn_bwd_dq_kernel<HD, NW>), grid, dim3(NW * 64), 2 * 128 * HD * 2, stream, p));
     return sf_check_launch("sf_attn_bwd_dq");
+}
+
+extern "C" int sf_attn_bwd_dq(const void* q, long ldq, const void* dout, long lddo, const void* k0, long ldk,
+                              const void* v0, long ldv, const int* kv_len, const float* lse,
+                              const float* delta, const float* dq_init, void* dq, long lddq, int B, int S, int nh,
+                              int nkv, int hd, float scale, void* stream) {
+    return attn_bwd_dq_entry(q, ldq, dout, lddo, k0, ldk, v0, ldv, kv_len, lse, delta, dq_init, dq, lddq, B, S, 0, nh, nkv, hd,
+                             scale, stream);
+}
+
+extern "C" int sf_attn_bwd_dq_off(const void* q, long ldq, const void* dout, long lddo, const void* k0, long ldk,
+                                  const void* v0, long ldv, const int* kv_len, const float* lse,
+                                  const float* delta, const float* dq_init, void* dq, long lddq, int B, int Sq, int q_off,
+                                  int nh, int nkv, int hd, float scale, void* stream) {
+    SF_CHECK_ARG(q_off >= 0 && (long)q_off + Sq <= 0x3fffffffL, "sf_attn_bwd_dq_off: q_off must be >= 0 (and q_off + Sq < 2^30)");
+    return attn_bwd_dq_entry(q, ldq, dout, lddo, k0, ldk, v0, ldv, kv_len, lse, delta, dq_init, dq, lddq, B, Sq, q_off, nh, nkv,
+                             hd, scale, stream);
 }

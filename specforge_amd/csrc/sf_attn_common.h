@@ -68,6 +68,7 @@ struct AttnFwdArgs {
     float scale;
     int l2_map;  // pair-major work order (attn_work_index); 0 only in the tools build's A/B
     int dbg;  // profiling experiments only (SF_ATTN_DBG): 1 = stage tile 0 only, 2 = skip the MFMA/softmax work
+    int q_off;   // ring shard: the S local queries sit at global positions q_off.. and k0 / v0 hold q_off + S rows per batch (see below)
 };
 
 struct AttnBwdArgs {
@@ -88,7 +89,12 @@ struct AttnBwdArgs {
     // (=, not +=) its partial gradients to part_k / part_v [hsplit][B*S, nkv*hd] fp32; attn_dkv_reduce_kernel adds them to dk / dv
     int hsplit;
     float* part_k; float* part_v; long part_stride;
+    int q_off;   // ring shard: as in AttnFwdArgs (k0 / v0 / dk / dv / part_k / part_v hold q_off + S rows per batch)
 };
+// Query offset (ring sequence parallelism).  With q_off > 0 the S query rows of a launch (q, o, dout, dq, lse, delta, the diagonal
+// branches) are the global positions [q_off, q_off + S) of a longer sequence whose step-0 keys k0 / v0 -- and their gradients dk / dv --
+// hold the rows [0, q_off + S): the causal bound of local query t is key q_off + t, kv_len counts global keys.  It is a wave-uniform
+// kernel argument used in loop bounds and mask tests only; with q_off = 0 a launch computes what it computed before the argument existed, bit for bit.
 
 // ---- LDS tile swizzle -------------------------------------------------------
 // 16-byte chunk c of tile row r is stored at chunk c ^ swz<HD>(r).  HD = 128 (16 chunks per 256-byte row):

@@ -129,13 +129,13 @@ SF_GLOBAL void SF_LAUNCH_BOUNDS(256, 1) attn_bwd_dkv_pair_kernel(AttnBwdArgs p) 
     const int kbi = bid / per_kb, g = gb % p.nkv, b = gb / p.nkv;
     const int hs = (int)blockIdx.x % hsplit;                // head split (small B * nkv), as in attn_bwd_dkv_kernel
     const int kb0 = kbi * KB;
-    const int S = p.S, nrep = (p.nh / p.nkv) / hsplit, h_first = g * (p.nh / p.nkv) + hs * nrep;
-    const int kvlen = p.kv_len ? p.kv_len[b] : S;
+    const int S = p.S, qo = p.q_off, SK = qo + S, nrep = (p.nh / p.nkv) / hsplit, h_first = g * (p.nh / p.nkv) + hs * nrep;
+    const int kvlen = p.kv_len ? p.kv_len[b] : SK;   // (local queries; keys [0, SK))
     if (kb0 >= kvlen) return;   // keys at / after kv_len never receive probability mass (workgroup-uniform; the reduce skips them too)
     const int kw0 = kb0 + sub * 32;
     const int ki = kw0 + c;     // this lane's key (column of S)
-    const bool kok = ki < S;
-    const long krow = (long)b * S + (kok ? ki : S - 1);
+    const bool kok = ki < SK;
+    const long krow = (long)b * SK + (kok ? ki : SK - 1);
     const float sc = p.scale * kLog2e;
     FragOff<HD> fo;
     fo.init(lane);
@@ -151,11 +151,11 @@ SF_GLOBAL void SF_LAUNCH_BOUNDS(256, 1) attn_bwd_dkv_pair_kernel(AttnBwdArgs p) 
         static_for<0, KS>([&](auto I) SF_LAMBDA_INLINE { bank.template set_f<decltype(I)::value>(ft[decltype(I)::value]); });
     }
 
-    const int qt_first = kb0 / QT, nqt = (S + QT - 1) / QT;
+    const int qt_first = (kb0 > qo ? kb0 - qo : 0) / QT, nqt = (S + QT - 1) / QT;
     const int per_head = nqt - qt_first, n_it = nrep * per_head;         // tiles, head-major (workgroup-uniform)
-    // a query q of the tile is visible to this lane's key iff  ki <= q < S  (and the key itself is valid): with
+    // a local query q of the tile is visible to this lane's key iff  ki <= qo + q  and  q < S  (and the key itself is valid): with
     // q = q0 + 4 * hi + C (C a compile-time constant per register) that is  lo <= C < up  for two per-tile values
-    const int key_lo = ki < kvlen ? ki : 0x3fffffff;
+    const int key_lo = ki < kvlen ? ki - qo : 0x3fffffff;
     TileStage<HD, QT, NW> stq, stdo;
     stq.init(p.ldq, wave, lane);
     stdo.init(p.lddo, wave, lane);
@@ -245,7 +245,7 @@ SF_GLOBAL void SF_LAUNCH_BOUNDS(256, 1) attn_bwd_dkv_pair_kernel(AttnBwdArgs p) 
         const char* q_p1 = q_ring + wc.slot * SLOT;                      // Q(n+1)
         const char* do_0 = do_ring + slot_do_0 * SLOT;                   // dO(n) | lse(n)
         const int q0_p1 = wc.qt * QT;
-        const bool lv_p1 = real(wc) && q0_p1 + QT - 1 >= kw0;
+        const bool lv_p1 = real(wc) && qo + q0_p1 + QT - 1 >= kw0;
         if (role == 0) {
             // ---- A: S(n+1) beside exp(n); then dV(n)
             const bool do_s = lv_p1, do_e = lv_0;
@@ -281,7 +281,7 @@ SF_GLOBAL void SF_LAUNCH_BOUNDS(256, 1) attn_bwd_dkv_pair_kernel(AttnBwdArgs p) 
                     }
                 };
             };
-            const bool need_mask = (q0 < kw0 + 32) || (kw0 + 31 >= kvlen) || (q0 + QT - 1 >= S);      // wave-uniform
+            const bool need_mask = (qo + q0 < kw0 + 32) || (kw0 + 31 >= kvlen) || (q0 + QT - 1 >= S);      // wave-uniform
             // S(n+1) = Q(n+1) . K^T beside exp(n); then dV^T += dO(n)^T . P(n)
             if (need_mask) pair_body<HD>(bank, do_s, do_e, q_p1, do_0, fo, s_next, f, fill_for(std::true_type{}), dma, all_pieces);
             else pair_body<HD>(bank, do_s, do_e, q_p1, do_0, fo, s_next, f, fill_for(std::false_type{}), dma, all_pieces);
@@ -354,7 +354,7 @@ int attn_bwd_dkv_w1_launch(const AttnBwdArgs& p, int hd, void* stream) {
     constexpr int HD = 256;
     constexpr int SMEM = (5 + 3) * (32 * HD * 2 + 256) + 2 * 2 * 32 * 32 * 4;      // Q ring, dO ring, exchange: 146 KiB
     const int hsplit = p.hsplit > 1 ? p.hsplit : 1;
-    dim3 grid((unsigned)((long)((p.S + 63) / 64) * p.nkv * p.B * hsplit));
+    dim3 grid((unsigned)((long)((p.q_off + p.S + 63) / 64) * p.nkv * p.B * hsplit));   // (key blocks)
     SF_ALLOW_SMEM((attn_bwd_dkv_pair_kernel<HD>), SMEM);
     SF_LAUNCH((attn_bwd_dkv_pair_kernel<HD>), grid, dim3(256), SMEM, stream, p);
     return 0;

@@ -90,10 +90,11 @@ class OnlineEagle3Model(nn.Module):
 
     def __init__(self, draft_model: LlamaForCausalLMEagle3, length: int = 7, attention_backend: str = "hip",
                  lk_loss_type: Optional[str] = None, kl_scale: float = 1.0, kl_decay: float = 1.0,
-                 ploss_decay: float = 0.8, sp_group=None):
+                 ploss_decay: float = 0.8, sp_group=None, sp_ulysses_group=None, sp_ring_group=None):
         """``attention_backend="usp"``: Ulysses sequence parallelism over ``sp_group`` (set here, or later by
         ``HipDPTrainingBackend.prepare_model`` / the strategy, before the first forward); every other value runs the one-rank
-        attention."""
+        attention.  ``sp_ring_group`` (with ``sp_ulysses_group``, None for a pure ring): ring x Ulysses over the same SP group
+        (training.make_usp_groups); ``sp_group`` alone is pure Ulysses."""
         super().__init__()
         if lk_loss_type not in (None, "alpha", "lambda"):
             raise ValueError(f"Unknown lk loss type: {lk_loss_type}")  # core/lk_loss.py:99
@@ -103,6 +104,7 @@ class OnlineEagle3Model(nn.Module):
         self.length = length
         self.attention_backend = attention_backend
         self.sp_group = sp_group
+        self.sp_ulysses_group, self.sp_ring_group = sp_ulysses_group, sp_ring_group
         self.lk_loss_type, self.kl_scale, self.kl_decay = lk_loss_type, kl_scale, kl_decay
         self.ploss_decay = ploss_decay
         self._engine: Optional[Eagle3Engine] = None
@@ -115,15 +117,15 @@ class OnlineEagle3Model(nn.Module):
         constructing it (algorithms/model_providers.py:268-275); adopting the parameters into the flat buffer any
         earlier would be undone by that move."""
         if self._engine is None:
-            sp_group = None
+            sp_group = uly_group = ring_group = None
             if self.attention_backend == "usp":
                 if self.sp_group is None:
                     raise ValueError("attention_backend 'usp' needs the SP process group (OnlineEagle3Model(sp_group=...), "
                                      "ParallelConfig(sp_size=...) or Eagle3TrainStrategy(sp_group=...))")
-                sp_group = self.sp_group
+                sp_group, uly_group, ring_group = self.sp_group, self.sp_ulysses_group, self.sp_ring_group
             self._engine = Eagle3Engine(self.draft_model, ttt_length=self.length, ploss_decay=self.ploss_decay,
                                         lk_loss_type=self.lk_loss_type, kl_scale=self.kl_scale, kl_decay=self.kl_decay,
-                                        sp_group=sp_group)
+                                        sp_group=sp_group, sp_ulysses_group=uly_group, sp_ring_group=ring_group)
             object.__setattr__(self.draft_model, "_hip_engine", self._engine)   # found by BF16Optimizer(draft_model)
         return self._engine
 
@@ -201,7 +203,7 @@ class Eagle3TrainStrategy:
 
     def __init__(self, eagle3_model: OnlineEagle3Model, *, target_head: Optional[TargetHead] = None,
                  ploss_decay: float = 0.8, compact_teacher: bool = True, compact_teacher_chunk_size: Optional[int] = None,
-                 pinned_staging: bool = True, sp_group=None):
+                 pinned_staging: bool = True, sp_group=None, sp_ulysses_group=None, sp_ring_group=None):
         """``pinned_staging=False`` (A/B only, ``bench.py --feed cpu_batch_pageable``): CPU batches are shifted on the CPU and
         moved with the blocking pageable ``.to(device)`` the reference's strategy uses (strategies/base.py:256-284)."""
         self.pinned_staging = pinned_staging
@@ -210,6 +212,8 @@ class Eagle3TrainStrategy:
             if eagle3_model._engine is not None and eagle3_model._engine.sp_group is not sp_group:
                 raise ValueError("sp_group must be set before the HIP engine is built (the first forward)")
             eagle3_model.sp_group = sp_group
+            if sp_ring_group is not None:   # ring x Ulysses (training.make_usp_groups)
+                eagle3_model.sp_ulysses_group, eagle3_model.sp_ring_group = sp_ulysses_group, sp_ring_group
         self.target_head = target_head
         self.ploss_decay = ploss_decay
         self._stager = None

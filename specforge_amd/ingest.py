@@ -56,7 +56,8 @@ def usp_shard(sample: Dict[str, torch.Tensor], *, ttt_length: int, sp_rank: int,
     """One sample's shard for Ulysses rank ``sp_rank`` of ``sp_size`` (data/preprocessing.py:446-521, ``process_data_usp``) from a
     normalised batch-1 sample (``normalize_offline_sample``: the global last loss-mask position is already zero): chunk =
     ceil(S / sp) rows from sp_rank * chunk plus ``ttt_length`` rows of overlap from the next shard, zero-padded past the sample's
-    end; attention_mask marks the real rows, position_ids the chunk's global positions."""
+    end; attention_mask marks the real rows, position_ids the chunk's global positions.  With ring attention (sp_size = u * r ranks,
+    training.make_usp_groups) sp_rank = ring_rank * u + ulysses_rank: the reference's shards for (ulysses_rank, ring_rank) are the same."""
     S = sample["input_ids"].shape[1]
     chunk = (S + sp_size - 1) // sp_size
     start, local = sp_rank * chunk, chunk + ttt_length

@@ -529,6 +529,42 @@ def attn_bwd_dkv(q, dout, k0, v0, kv_len, lse, delta, dk, dv, *, B, S, nh, nkv, 
                                  _stream()), "sf_attn_bwd_dkv")
 
 
+# ---- query offset (ring sequence parallelism; include/specforge_amd.h: sf_attn_fwd_off): ``S`` = the local query count, q / o / dout /
+# dq / lse / delta / kd / vd hold those rows; k0 / v0 / dk / dv hold the ``q_off + S`` global key rows per batch
+
+
+def attn_fwd_off(q, k0, v0, kd: List[torch.Tensor], vd: List[torch.Tensor], kv_len, o, lse, *, B, S, q_off, nh, nkv, hd, scale):
+    L = _lib.lib()
+    ldk = _rowmajor(k0)
+    for t in [v0] + list(kd) + list(vd):
+        assert _rowmajor(t) == ldk
+    _lib.check(L.sf_attn_fwd_off(_p(q), _rowmajor(q), _p(k0), ldk, _p(v0), _ptr_array(kd), _ptr_array(vd), len(kd),
+                                 _p(kv_len), _p(o), _rowmajor(o), _p(lse), B, S, q_off, nh, nkv, hd, scale, _stream()),
+               "sf_attn_fwd_off")
+
+
+def attn_bwd_dq_off(q, dout, k0, v0, kv_len, lse, delta, dq_init, dq, *, B, S, q_off, nh, nkv, hd, scale):
+    L = _lib.lib()
+    _lib.check(L.sf_attn_bwd_dq_off(_p(q), _rowmajor(q), _p(dout), _rowmajor(dout), _p(k0), _rowmajor(k0), _p(v0),
+                                    _rowmajor(v0), _p(kv_len), _p(lse), _p(delta), _p(dq_init), _p(dq),
+                                    _rowmajor(dq), B, S, q_off, nh, nkv, hd, scale, _stream()), "sf_attn_bwd_dq_off")
+
+
+def attn_bwd_dkv_off_workspace_floats(B, S, q_off, nh, nkv, hd) -> int:
+    """fp32 workspace the head-split form of attn_bwd_dkv_off wants (it follows the q_off + S key rows)"""
+    return int(_lib.lib().sf_attn_bwd_dkv_off_workspace_floats(B, S, q_off, nh, nkv, hd))
+
+
+def attn_bwd_dkv_off(q, dout, k0, v0, kv_len, lse, delta, dk, dv, *, B, S, q_off, nh, nkv, hd, scale, workspace=None):
+    L = _lib.lib()
+    assert dk.dtype == torch.float32 and dv.dtype == torch.float32 and _rowmajor(dk) == _rowmajor(dv)
+    assert workspace is None or (workspace.dtype == torch.float32 and workspace.is_contiguous())
+    _lib.check(L.sf_attn_bwd_dkv_off(_p(q), _rowmajor(q), _p(dout), _rowmajor(dout), _p(k0), _rowmajor(k0),
+                                     _p(v0), _rowmajor(v0), _p(kv_len), _p(lse), _p(delta), _p(dk), _p(dv), _rowmajor(dk),
+                                     B, S, q_off, nh, nkv, hd, scale, _p(workspace), workspace.numel() if workspace is not None else 0,
+                                     _stream()), "sf_attn_bwd_dkv_off")
+
+
 def grad_norm(g: torch.Tensor, norm_out: torch.Tensor, workspace: torch.Tensor, prescale: float = 1.0):
     L = _lib.lib()
     assert g.is_contiguous() and workspace.numel() >= L.sf_grad_norm_workspace_floats()

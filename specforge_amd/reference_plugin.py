@@ -84,11 +84,12 @@ class HipEagle3TrainStrategy(Eagle3TrainStrategy):
 def check_training_topology(t, draft_config=None) -> None:
     """Refuse, before any step, the training topologies the HIP path does not implement (config/schema.py:523-531,590-604): they
     would otherwise train each rank's shard as if it were a whole sample.  Ulysses SP runs on ``Eagle3Engine``'s USP mode through the
-    Python API (``HipDPTrainingBackend(ParallelConfig(sp_size=N))`` + ``HiddenStateIngest(sp_rank=, sp_size=)``); this plugin does
-    not wire its loader and groups, so ``attention_backend: usp`` is refused here too -- after the checks that name a specific key."""
+    Python API (``HipDPTrainingBackend(ParallelConfig(sp_size=N, sp_ring_size=R))`` + ``HiddenStateIngest(sp_rank=, sp_size=)``); this
+    plugin does not wire its loader and groups, so ``attention_backend: usp`` is refused here too -- after the checks that name a specific
+    key."""
     if int(getattr(t, "sp_ring_size", 1) or 1) > 1:
-        raise ValueError(f"training.sp_ring_size = {t.sp_ring_size}: ring attention is not implemented by the HIP path "
-                         "(use sp_ulysses_size alone)")
+        raise ValueError(f"training.sp_ring_size = {t.sp_ring_size}: this plugin does not wire sequence parallelism; ring attention runs "
+                         "through the Python API (HipDPTrainingBackend(ParallelConfig(sp_size=..., sp_ring_size=...)))")
     if int(getattr(t, "tp_size", 1) or 1) > 1:
         raise ValueError(f"training.tp_size = {t.tp_size}: tensor parallelism is not implemented by the HIP path")
     if getattr(t, "attention_backend", None) != "usp":

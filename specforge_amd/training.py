@@ -191,6 +191,16 @@ class ParallelConfig:
     dp_size: int = 1
     sharding_strategy: str = "NO_SHARD"
     fsdp_process_group: Any = None
+    sp_ring_size: int = 1       # ring degree inside sp_size: sp_size = sp_ulysses_size * sp_ring_size
+
+    def __post_init__(self):
+        if int(self.sp_ring_size) < 1 or int(self.sp_size) % int(self.sp_ring_size):
+            raise ValueError(f"sp_ring_size {self.sp_ring_size} must divide sp_size {self.sp_size} "
+                             "(sp_size = sp_ulysses_size * sp_ring_size)")
+
+    @property
+    def sp_ulysses_size(self) -> int:
+        return int(self.sp_size) // int(self.sp_ring_size)
 
 
 def make_sp_groups(sp_size: int):
@@ -209,6 +219,33 @@ def make_sp_groups(sp_size: int):
         if rank % sp_size == j:
             dp_group = g
     return sp_group, dp_group
+
+
+def make_usp_groups(sp_size: int, sp_ring_size: int = 1):
+    """(sp_group, ulysses_group, ring_group, draft_dp_group) of this rank: make_sp_groups' mesh, each SP group of u * r consecutive ranks
+    split as the reference's set_seq_parallel_pg does (distributed.py:133-195) -- Ulysses peers consecutive, sp_rank = ring_rank * u +
+    ulysses_rank.  ulysses_group is None when u = 1 (pure ring), ring_group None when r = 1.  Every rank creates every group, in the
+    same order."""
+    if sp_ring_size < 1 or sp_size % sp_ring_size:
+        raise ValueError(f"sp_ring_size {sp_ring_size} must divide sp_size {sp_size}")
+    sp_group, dp_group = make_sp_groups(sp_size)
+    world, rank = dist.get_world_size(), dist.get_rank()
+    u, r = sp_size // sp_ring_size, sp_ring_size
+    uly_group = ring_group = None
+    if r > 1:
+        for i in range(world // sp_size):
+            base = i * sp_size
+            for t in range(r):
+                g = dist.new_group([base + t * u + j for j in range(u)]) if u > 1 else None
+                if u > 1 and rank // sp_size == i and (rank - base) // u == t:
+                    uly_group = g
+            for j in range(u):
+                g = dist.new_group([base + t * u + j for t in range(r)])
+                if rank // sp_size == i and (rank - base) % u == j:
+                    ring_group = g
+    else:
+        uly_group = sp_group
+    return sp_group, uly_group, ring_group, dp_group
 
 
 class HipDPTrainingBackend:
@@ -237,8 +274,11 @@ class HipDPTrainingBackend:
         self.sp_size = int(self.parallel_config.sp_size)
         if self.parallel_config.tp_size > 1:
             raise ValueError(f"tp_size {self.parallel_config.tp_size}: tensor parallelism is not implemented by the HIP path")
-        self.sp_group = self.draft_dp_group = None
-        if self.sp_size > 1:
+        self.sp_ring_size = int(getattr(self.parallel_config, "sp_ring_size", 1) or 1)
+        self.sp_group = self.draft_dp_group = self.sp_ulysses_group = self.sp_ring_group = None
+        if self.sp_ring_size > 1:       # ring (x Ulysses): the SP group split into its Ulysses and ring subgroups
+            self.sp_group, self.sp_ulysses_group, self.sp_ring_group, self.draft_dp_group = make_usp_groups(self.sp_size, self.sp_ring_size)
+        elif self.sp_size > 1:
             self.sp_group, self.draft_dp_group = make_sp_groups(self.sp_size)
 
     @property
@@ -256,6 +296,8 @@ class HipDPTrainingBackend:
             if model._engine is not None and model._engine.sp_group is not self.sp_group:
                 raise ValueError("sp_size must be set before the HIP engine is built (the first forward)")
             model.sp_group = self.sp_group
+            if self.sp_ring_size > 1:
+                model.sp_ulysses_group, model.sp_ring_group = self.sp_ulysses_group, self.sp_ring_group
         use_dp = self.world > 1 or (self._force_collectives and dist.is_available() and dist.is_initialized())
         model.engine.on_bucket_ready = self._bucket_ready if use_dp else None
         if use_dp:  # replicas must start identical (DDP broadcasts rank 0's parameters)
