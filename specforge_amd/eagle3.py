@@ -194,6 +194,23 @@ class TargetHead(nn.Module):
         return padding_left_shift(input_ids), padding_left_shift(target), loss_mask[..., None]
 
 
+def usp_unpad(tensors):
+    """A USP shard as the engine takes it: ``chunk + ttt_length`` rows.  The reference's collator (data/utils.py:122-196) pads
+    ``input_ids``, ``attention_mask``, ``loss_mask`` and ``target`` of a shard to a multiple of the SP degree but not ``hidden_state``, and
+    its model reads the local length from ``hidden_state`` (eagle3/model.py:310, core/eagle3_adapters.py:98-140); the rows past it are
+    zeros.  Shards without that padding (``ingest.usp_shard``) come back unchanged."""
+    hs = tensors.get("hidden_state")
+    if hs is None:
+        return tensors
+    n = hs.shape[1]
+    out = dict(tensors)
+    for k in ("input_ids", "attention_mask", "loss_mask", "target"):
+        v = out.get(k)
+        if v is not None and v.dim() >= 2 and v.shape[1] > n:
+            out[k] = v[:, :n]
+    return out
+
+
 class Eagle3TrainStrategy:
     """training/strategies/base.py:124-319.  The teacher always runs the streaming path
     (target hidden state + frozen head weight -> soft targets; [B,S,V_target] is never kept)."""
@@ -244,15 +261,18 @@ class Eagle3TrainStrategy:
 
     def forward_loss(self, batch, ctx=None) -> StepOutput:
         self.validate_batch(batch)
+        tensors = batch.tensors
+        if self.eagle3_model.attention_backend == "usp":
+            tensors = usp_unpad(tensors)
         # rows per TTT step that carry a loss (host integers): from the loader's metadata, or from the mask while it is still a CPU tensor
         md = getattr(batch, "metadata", None) or {}
         counts = md.get("loss_mask_suffix_counts")
-        lm0 = batch.tensors.get("loss_mask")
+        lm0 = tensors.get("loss_mask")
         if counts is None and lm0 is not None and not lm0.is_cuda:
             counts = loss_mask_suffix_counts(lm0)
-        pid0 = batch.tensors.get("position_ids")
+        pid0 = tensors.get("position_ids")
         span = (int(pid0.min()), int(pid0.max())) if pid0 is not None and not pid0.is_cuda and pid0.numel() else None
-        t = self._resident(batch.tensors)
+        t = self._resident(tensors)
         target_repr = md.get("target_repr")
         kwargs = {}
         if target_repr == "hidden_state":

@@ -165,7 +165,7 @@ class _Slot:
             n *= x
         return self.d[k][:n].view(shape)
 
-    def __init__(self, B, L, Ht, device, pin):
+    def __init__(self, B, L, Ht, device, pin, pos_len: int = 0):
         def host(*shape, dtype):
             t = torch.zeros(*shape, dtype=dtype)
             return t.pin_memory() if pin else t
@@ -173,6 +173,8 @@ class _Slot:
         self.h = dict(input_ids=host(B, L, dtype=torch.int64), attention_mask=host(B, L, dtype=torch.int64),
                       loss_mask=host(B, L, dtype=torch.int64), hidden_state=host(B, L, 3 * Ht, dtype=torch.bfloat16),
                       target=host(B, L, Ht, dtype=torch.bfloat16))
+        if pos_len:     # USP shards carry their global positions
+            self.h["position_ids"] = host(B, pos_len, dtype=torch.int64)
         # device side: flat buffers, viewed as a CONTIGUOUS [B, L, ...] tensor of the batch's actual padded length
         self.d = {k: torch.zeros(v.numel(), dtype=v.dtype, device=device) for k, v in self.h.items()} if device.type == "cuda" else None
         self.copied = None      # event on the copy stream: H2D of this slot finished
@@ -185,15 +187,21 @@ _LAYOUT_CACHE_MAX = 1 << 16     # entries; a multi-million-file dataset must not
 class HiddenStateIngest:
     def __init__(self, files: Sequence[str], *, batch_size: int, max_len: int, target_hidden_size: Optional[int] = None, device="cuda",
                  dp_rank: int = 0, dp_size: int = 1, seed: int = 0, shuffle: bool = True, pad_multiple: int = 1,
-                 slots: int = 2, reader_threads: int = 4, direct: bool = True, sp_rank: int = 0, sp_size: int = 1, ttt_length: int = 7):
+                 slots: int = 2, reader_threads: int = 4, direct: bool = True, sp_rank: int = 0, sp_size: int = 1, ttt_length: int = 7,
+                 collator_layout: bool = False, sp_ulysses_size: Optional[int] = None):
         """``target_hidden_size=None``: taken from the first file read (the reference's loader does not know it either).
         ``sp_size > 1`` (attention_backend "usp"): every batch is this SP rank's shard of one sample (``usp_shard``); ``dp_rank`` /
-        ``dp_size`` are then the DRAFT-DP rank and size, so the sp peers of a group read the same sample (launch.py:177-205)."""
+        ``dp_size`` are then the DRAFT-DP rank and size, so the sp peers of a group read the same sample (launch.py:177-205).  The direct
+        reader then reads only the shard's ``chunk + ttt_length`` rows of every tensor from the file (``_read_shard_direct``).
+        ``collator_layout``: shards laid out as the reference's ``DataCollatorWithPadding`` returns them under SP (data/utils.py:122-196):
+        ids, masks and target zero-padded to a multiple of ``sp_size``, position ids to that length times ``sp_ulysses_size``."""
         if sp_size > 1 and batch_size != 1:
             raise ValueError("batch_size must be 1 with attention_backend 'usp'")
         if not 0 <= sp_rank < sp_size:
             raise ValueError(f"sp_rank {sp_rank} outside 0..{sp_size - 1}")
         self.sp_rank, self.sp_size, self.ttt_length = sp_rank, sp_size, ttt_length
+        self.collator_layout = bool(collator_layout)
+        self.sp_ulysses_size = int(sp_ulysses_size or sp_size)
         self.files = list(files)
         self.B, self.max_len, self.Ht = batch_size, max_len, target_hidden_size
         self.device = torch.device(device)
@@ -201,6 +209,12 @@ class HiddenStateIngest:
         self.pad_multiple = pad_multiple
         cuda = self.device.type == "cuda"
         self._Lcap = (max_len + pad_multiple - 1) // pad_multiple * pad_multiple
+        self._pos_cap = 0
+        if sp_size > 1:     # a shard: chunk = ceil(S / sp) <= ceil(max_len / sp) rows plus the overlap, padded as the collator pads
+            local = (max_len + sp_size - 1) // sp_size + ttt_length
+            local = (local + sp_size - 1) // sp_size * sp_size
+            self._Lcap = max(self._Lcap, local)
+            self._pos_cap = local * self.sp_ulysses_size if self.collator_layout else local
         self._nslots = max(2, slots)
         self._slots: List[_Slot] = []
         self._copy_stream = torch.cuda.Stream(device=self.device) if cuda else None
@@ -221,7 +235,7 @@ class HiddenStateIngest:
             else:
                 self.Ht = int(torch.load(first_path, mmap=True, weights_only=True)["hidden_state"].shape[-1])
         cuda = self.device.type == "cuda"
-        self._slots = [_Slot(self.B, self._Lcap, self.Ht, self.device, pin=cuda) for _ in range(self._nslots)]
+        self._slots = [_Slot(self.B, self._Lcap, self.Ht, self.device, pin=cuda, pos_len=self._pos_cap) for _ in range(self._nslots)]
 
     def batches_per_epoch(self) -> int:
         n = len(distributed_sampler_indices(len(self.files), dp_rank=self.dp_rank, dp_size=self.dp_size, seed=self.seed,
@@ -279,6 +293,78 @@ class HiddenStateIngest:
             slot.h["loss_mask"][b, n - 1] = 0
         slot.h["attention_mask"][b, :n] = 1
         return n
+
+    def _shard_lengths(self, n: int) -> Dict[str, int]:
+        """rows of every staged tensor of this rank's shard of an n-row sample"""
+        chunk = (n + self.sp_size - 1) // self.sp_size
+        local = chunk + self.ttt_length
+        if not self.collator_layout:
+            return dict(hidden_state=local, target=local, input_ids=local, loss_mask=local, attention_mask=local, position_ids=chunk)
+        lpad = (local + self.sp_size - 1) // self.sp_size * self.sp_size
+        return dict(hidden_state=local, target=lpad, input_ids=lpad, loss_mask=lpad, attention_mask=lpad,
+                    position_ids=lpad * self.sp_ulysses_size)
+
+    def _read_shard_direct(self, slot: _Slot, path: str) -> Optional[Dict[str, int]]:
+        """this SP rank's shard of the sample (``usp_shard`` of the normalised sample) -> row 0 of the slot, reading from the file only
+        the rows [start, start + chunk + ttt_length) of every tensor; the zero tail past the sample's end is written in place.  Returns
+        the staged lengths, or None if the file needs the generic path."""
+        lay = self._layout(path)
+        if lay is None or any(src not in lay for _, src in self._SOURCE):
+            return None
+        n, plan = None, []
+        for dst, src in self._SOURCE:
+            off, dtype, shape = lay[src]
+            buf = slot.h[dst]
+            hidden = buf.dim() == 3
+            if dtype != buf.dtype or (hidden and not (len(shape) == 3 and shape[0] == 1 and shape[2] == buf.shape[-1])) \
+                    or (not hidden and len(shape) != 1):
+                return None
+            rows, feat = (shape[1], shape[2]) if hidden else (shape[0], 1)
+            if n is not None and min(rows, self.max_len) != n:
+                return None
+            n = min(rows, self.max_len)
+            plan.append((dst, off, feat * buf.element_size()))
+        lens = self._shard_lengths(n)
+        chunk = (n + self.sp_size - 1) // self.sp_size
+        start = self.sp_rank * chunk
+        valid = max(min(start + chunk + self.ttt_length, n) - start, 0)
+        fd = os.open(path, os.O_RDONLY)
+        try:
+            for dst, off, row_bytes in plan:
+                buf = slot.h[dst]
+                nbytes = valid * row_bytes
+                view, done, base = (_bytes_view(buf[0, :valid]) if valid else None), 0, off + start * row_bytes
+                while done < nbytes:       # preadv may legally return fewer bytes (network / FUSE filesystems, signals)
+                    got = os.preadv(fd, [view[done:]], base + done)
+                    if got <= 0:
+                        return None        # truncated file: let torch.load produce the error (or read it)
+                    done += got
+                buf[0, valid:lens[dst]].zero_()
+        finally:
+            os.close(fd)
+        if start <= n - 1 < start + valid:     # the sample's last loss-mask position (normalize_offline_sample)
+            slot.h["loss_mask"][0, n - 1 - start] = 0
+        am = slot.h["attention_mask"]
+        am[0, :valid] = 1
+        am[0, valid:lens["attention_mask"]] = 0
+        pos = slot.h["position_ids"]
+        torch.arange(start, start + chunk, out=pos[0, :chunk])
+        pos[0, chunk:lens["position_ids"]] = 0
+        return lens
+
+    def _read_shard_generic(self, slot: _Slot, path: str) -> Dict[str, int]:
+        full = normalize_offline_sample(torch.load(path, mmap=True, weights_only=True), self.max_len)
+        lens = self._shard_lengths(full["input_ids"].shape[1])
+        s = usp_shard(full, ttt_length=self.ttt_length, sp_rank=self.sp_rank, sp_size=self.sp_size)
+        for k, buf in slot.h.items():
+            m = s[k].shape[1]
+            buf[0, :m].copy_(s[k][0])
+            buf[0, m:lens[k]].zero_()
+        return lens
+
+    def _fill_shard(self, slot: _Slot, path: str) -> Dict[str, int]:
+        lens = self._read_shard_direct(slot, path) if self._direct else None
+        return lens if lens is not None else self._read_shard_generic(slot, path)
 
     def _read_generic(self, slot: _Slot, b: int, path: str) -> int:
         s = normalize_offline_sample(torch.load(path, mmap=True, weights_only=True), self.max_len)
@@ -362,12 +448,16 @@ class HiddenStateIngest:
                     slot = self._slots[si]
                     if slot.released is not None:      # the consumer's stream must be past this slot's tensors
                         slot.released.synchronize()
-                    L = self._fill(slot, g)
-                    counts = loss_mask_suffix_counts(slot.h["loss_mask"][:len(g), :L])   # (host side: the engine's loss-row compaction)
+                    if self.sp_size > 1:    # this rank's shard, read as such (the engine's USP mode takes no suffix counts)
+                        L, counts = self._fill_shard(slot, g[0]), None
+                    else:
+                        L = self._fill(slot, g)
+                        counts = loss_mask_suffix_counts(slot.h["loss_mask"][:len(g), :L])   # (host side: the engine's loss-row compaction)
                     if self._copy_stream is not None:
                         with torch.cuda.stream(self._copy_stream):
                             for k in slot.h:
-                                slot.dview(k, L)[:len(g)].copy_(slot.h[k][:len(g), :L], non_blocking=True)
+                                Lk = L[k] if counts is None else L
+                                slot.dview(k, Lk)[:len(g)].copy_(slot.h[k][:len(g), :Lk], non_blocking=True)
                             slot.copied = torch.cuda.Event()
                             slot.copied.record()
                     ready.put((si, L, g, counts))
@@ -396,14 +486,19 @@ class HiddenStateIngest:
                 nb = len(g)
                 if self._copy_stream is not None:
                     torch.cuda.current_stream().wait_event(slot.copied)
-                    tensors = {k: slot.dview(k, L)[:nb] for k in slot.d}
+                if counts is None:          # a USP shard: per-tensor lengths
+                    if self._copy_stream is not None:
+                        tensors = {k: slot.dview(k, L[k])[:nb] for k in slot.d}
+                    else:
+                        tensors = {k: v[:nb, :L[k]].clone() for k, v in slot.h.items()}
+                    md = {"target_repr": "hidden_state", "sample_files": list(g)}
                 else:
-                    tensors = {k: v[:nb, :L].clone() for k, v in slot.h.items()}
+                    if self._copy_stream is not None:
+                        tensors = {k: slot.dview(k, L)[:nb] for k in slot.d}
+                    else:
+                        tensors = {k: v[:nb, :L].clone() for k, v in slot.h.items()}
+                    md = {"target_repr": "hidden_state", "sample_files": list(g), "loss_mask_suffix_counts": counts}
                 prev = si
-                md = {"target_repr": "hidden_state", "sample_files": list(g), "loss_mask_suffix_counts": counts}
-                if self.sp_size > 1:        # (the engine's USP mode runs the dense lm_head: no suffix counts for the shard)
-                    tensors = usp_shard(tensors, ttt_length=self.ttt_length, sp_rank=self.sp_rank, sp_size=self.sp_size)
-                    del md["loss_mask_suffix_counts"]
                 yield TrainBatch(tensors, md)
         finally:
             # the consumer may abandon the iterator mid-epoch (max_steps reached): release the loader thread

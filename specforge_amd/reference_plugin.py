@@ -23,8 +23,9 @@ executable; nothing else in ``specforge_amd`` imports it).  It provides, each at
   the files' bytes read straight into the pinned slot) -- same refs, same order, same ``seek`` / ``set_epoch`` /
   ``drop_last`` behaviour (feature_dataloader.py:255-295), tensors bit-identical to the reference's normaliser +
   collator.  Anything the fast reader does not cover (``.ckpt.gz``, ``mem://`` refs, another algorithm's transform or
-  collator, USP collation) is materialised by the reference's own ``_make_batch`` on a loader thread and staged through
-  the same pinned slots.
+  collator) is materialised by the reference's own ``_make_batch`` on a loader thread and staged through the same pinned
+  slots.  Under ``attention_backend: usp`` the reference's ``process_data_usp`` + collator are served by the ranged reader:
+  each SP rank reads only its shard's rows of every tensor (``HiddenStateIngest(sp_rank=, sp_size=, collator_layout=True)``).
 """
 from __future__ import annotations
 
@@ -81,29 +82,44 @@ class HipEagle3TrainStrategy(Eagle3TrainStrategy):
     name = ALGORITHM_NAME   # the checkpoint's ``strategy`` field must equal the algorithm name (training/trainer.py:288)
 
 
-def check_training_topology(t, draft_config=None) -> None:
-    """Refuse, before any step, the training topologies the HIP path does not implement (config/schema.py:523-531,590-604): they
-    would otherwise train each rank's shard as if it were a whole sample.  Ulysses SP runs on ``Eagle3Engine``'s USP mode through the
-    Python API (``HipDPTrainingBackend(ParallelConfig(sp_size=N, sp_ring_size=R))`` + ``HiddenStateIngest(sp_rank=, sp_size=)``); this
-    plugin does not wire its loader and groups, so ``attention_backend: usp`` is refused here too -- after the checks that name a specific
-    key."""
-    if int(getattr(t, "sp_ring_size", 1) or 1) > 1:
-        raise ValueError(f"training.sp_ring_size = {t.sp_ring_size}: this plugin does not wire sequence parallelism; ring attention runs "
-                         "through the Python API (HipDPTrainingBackend(ParallelConfig(sp_size=..., sp_ring_size=...)))")
+USP_HEAD_DIMS = (64, 128, 256)     # the head_dims the USP path runs natively (no zero-padded heads under the all-to-all)
+
+
+def check_training_topology(t, draft_config=None, mode=None) -> None:
+    """Refuse the training topologies the HIP path does not implement, each with a ``ValueError`` naming its key
+    (config/schema.py:523-531,590-604,879-881).  ``t`` is ``config.training``, ``draft_config`` the draft's config (HF object, dict
+    or ``DraftConfig``; the head checks are skipped without it), ``mode`` the run's ``config.mode``.
+
+    ``attention_backend: usp`` with ``sp_ulysses_size * sp_ring_size > 1`` is accepted in offline mode: ``specforge train`` builds the
+    reference's groups, the backend adopts them and the loader shards each sample over them.  Called by ``main()``
+    right after the run YAML is loaded -- before any process group or engine exists -- and again by the model factory."""
     if int(getattr(t, "tp_size", 1) or 1) > 1:
         raise ValueError(f"training.tp_size = {t.tp_size}: tensor parallelism is not implemented by the HIP path")
     if getattr(t, "attention_backend", None) != "usp":
         return
     if int(getattr(t, "batch_size", 1) or 1) != 1:
         raise ValueError("training.batch_size must be 1 with attention_backend 'usp'")
-    sp = int(getattr(t, "sp_ulysses_size", 1) or 1)
+    u = int(getattr(t, "sp_ulysses_size", 1) or 1)
+    r = int(getattr(t, "sp_ring_size", 1) or 1)
+    if u * r <= 1:
+        raise ValueError(f"attention_backend 'usp' needs training.sp_ulysses_size * training.sp_ring_size > 1 (got {u} x {r})")
     if draft_config is not None:
         c = draft_config if isinstance(draft_config, DraftConfig) else DraftConfig.from_hf(draft_config)
-        if c.num_attention_heads % sp or c.num_key_value_heads % sp:
-            raise ValueError(f"training.sp_ulysses_size {sp} must divide num_attention_heads ({c.num_attention_heads}) and "
+        if c.num_attention_heads % u or c.num_key_value_heads % u:
+            raise ValueError(f"training.sp_ulysses_size {u} must divide num_attention_heads ({c.num_attention_heads}) and "
                              f"num_key_value_heads ({c.num_key_value_heads})")
-    raise ValueError("training.attention_backend 'usp': the plugin's loader does not shard samples over the SP ranks; drive USP through "
-                     "the Python API (HipDPTrainingBackend(ParallelConfig(sp_size=...)), HiddenStateIngest(sp_rank=..., sp_size=...))")
+        rs = c.rope_scaling or {}
+        if rs.get("rope_type", rs.get("type")) == "mrope":
+            raise ValueError("rope_scaling.rope_type 'mrope' is not supported with attention_backend 'usp' (the reference refuses it "
+                             "too, llama3_eagle.py:1363-1505)")
+        hd = c.head_dim or c.hidden_size // c.num_attention_heads
+        if hd not in USP_HEAD_DIMS:
+            raise ValueError(f"head_dim {hd}: attention_backend 'usp' needs a native head_dim {USP_HEAD_DIMS}")
+    if mode != "offline":
+        raise ValueError(f"training.attention_backend 'usp' (training.sp_ulysses_size = {u}, training.sp_ring_size = {r}) trains on "
+                         f"offline features only (mode {mode!r}; the reference refuses other modes too, config/schema.py:879-881).  "
+                         "Outside a run config, drive USP through the Python API (HipDPTrainingBackend(ParallelConfig(sp_size=..., "
+                         "sp_ring_size=...)), HiddenStateIngest(sp_rank=..., sp_size=...))")
 
 
 def _training_model_factory():
@@ -114,7 +130,7 @@ def _training_model_factory():
     def build(config, draft_model, draft_config, target_config, _tokenizer):
         """``build_eagle3_model`` (algorithms/model_providers.py:255-291) with the HIP composite"""
         t = config.training
-        check_training_topology(t, draft_config)
+        check_training_topology(t, draft_config, mode=getattr(config, "mode", None))
         model = OnlineEagle3Model(draft_model=draft_model, length=t.ttt_length, attention_backend=t.attention_backend,
                                   lk_loss_type=t.lk_loss_type, kl_scale=t.kl_scale, kl_decay=t.kl_decay)
         model = model.to(device=mp._device(), dtype=mp._torch_dtype(config))
@@ -216,23 +232,48 @@ def feature_loader_class():
     import functools
 
     from specforge.algorithms.eagle3.data import normalize_offline_sample as ref_normalize
+    from specforge.data.preprocessing import OfflineEagle3Dataset
     from specforge.data.utils import DataCollatorWithPadding
     from specforge.runtime.contracts import TrainBatch as RefTrainBatch
     from specforge.runtime.data_plane.feature_dataloader import FeatureDataLoader
 
     from .ingest import HiddenStateIngest, PinnedStager
 
+    ref_usp = OfflineEagle3Dataset.process_data_usp
+
     class HipFeatureDataLoader(FeatureDataLoader):
         _ingest = None
         _stager = None
 
-        def _fast_max_len(self, chunks):
-            """max_len when every batch is plain EAGLE3 offline files through the reference's eagle3 normaliser and
-            padding collator (what ``HiddenStateIngest`` is pinned to, tests/golden/ingest_collate.pt); else None"""
+        def _usp_plan(self):
+            """(max_len, ttt_length, sp_rank, sp_size, ulysses_size) when the transform is the reference's USP shard
+            (``process_data_usp`` as ``build_offline_normalizer(use_usp_preprocess=True)`` binds it, algorithms/eagle3/data.py:52-80) with
+            the rank convention of ``ingest.usp_shard`` and the collator pads for the same degrees; else None"""
             t, c = self.per_sample_transform, self.collate_fn
-            if not (isinstance(t, functools.partial) and t.func is ref_normalize and not t.args and set(t.keywords) == {"max_len"}):
+            if not (isinstance(t, functools.partial) and t.func is ref_usp and not t.args
+                    and set(t.keywords) == {"max_len", "ttt_length", "sp_rank", "sp_size", "ring_rank", "sp_ring_size"}):
                 return None
-            if type(c) is not DataCollatorWithPadding or getattr(c, "sp_degree", 1) != 1 or getattr(c, "ulysses_degree", 1) != 1:
+            k = t.keywords
+            sp, r = int(k["sp_size"]), int(k["sp_ring_size"])
+            if sp < 2 or r < 1 or sp % r:
+                return None
+            u = sp // r
+            if int(k["sp_rank"]) // u != int(k["ring_rank"]) or type(c) is not DataCollatorWithPadding \
+                    or getattr(c, "sp_degree", 1) != sp or getattr(c, "ulysses_degree", 1) != u:
+                return None
+            return int(k["max_len"]), int(k["ttt_length"]), int(k["sp_rank"]), sp, u
+
+        def _fast_max_len(self, chunks, usp=None):
+            """max_len when every batch is plain EAGLE3 offline files through the reference's eagle3 normaliser (or, ``usp`` given, its
+            USP shard: one sample per batch) and padding collator (what ``HiddenStateIngest`` is pinned to,
+            tests/golden/ingest_collate.pt); else None"""
+            t, c = self.per_sample_transform, self.collate_fn
+            if usp is not None:
+                if any(len(chunk) != 1 for chunk in chunks):
+                    return None
+            elif not (isinstance(t, functools.partial) and t.func is ref_normalize and not t.args and set(t.keywords) == {"max_len"}):
+                return None
+            elif type(c) is not DataCollatorWithPadding or getattr(c, "sp_degree", 1) != 1 or getattr(c, "ulysses_degree", 1) != 1:
                 return None
             keys = {"input_ids", "loss_mask", "hidden_state", "aux_hidden_state"}
             for chunk in chunks:
@@ -241,7 +282,22 @@ def feature_loader_class():
                     if not u.startswith("file://") or u.endswith(".gz") or set(r.feature_keys) != keys \
                             or any(k != v for k, v in r.feature_keys.items()):
                         return None
-            return int(t.keywords["max_len"])
+            return usp[0] if usp is not None else int(t.keywords["max_len"])
+
+        def _iter_usp(self, chunks, dev, usp):
+            """one SP rank's shards (refs already sampled over draft-dp by the reference, launch.py:174-211): the ranged direct reader
+            reads only this rank's rows; batches laid out as ``process_data_usp`` + the collator make them"""
+            max_len, ttt, sp_rank, sp, u = usp
+            ing = self._ingest
+            if ing is None or ing.max_len != max_len or ing.device != dev or ing.sp_size != sp or ing.sp_rank != sp_rank \
+                    or ing.ttt_length != ttt or ing.sp_ulysses_size != u or not ing.collator_layout:
+                ing = self._ingest = HiddenStateIngest([], batch_size=1, max_len=max_len, device=dev, sp_rank=sp_rank, sp_size=sp,
+                                                       ttt_length=ttt, collator_layout=True, sp_ulysses_size=u)
+            groups = [[r.feature_store_uri[len("file://"):] for r in chunk] for chunk in chunks]
+            for chunk, b in zip(chunks, ing.stream(groups)):
+                yield RefTrainBatch(sample_ids=[r.sample_id for r in chunk], strategy=self.strategy, tensors=b.tensors,
+                                    metadata={"target_repr": chunk[0].metadata.get("target_repr"),
+                                              "ttt_length": chunk[0].metadata.get("ttt_length")})
 
         def _iter_refs(self):
             skip, self._seek_batches = self._seek_batches, 0        # feature_dataloader.py:257-266
@@ -254,12 +310,16 @@ def feature_loader_class():
             if not chunks:
                 return
             dev = _device_for_batches()
-            max_len = self._fast_max_len(chunks)
+            usp = self._usp_plan()
+            max_len = self._fast_max_len(chunks, usp)
             if max_len is None:
                 yield from self._iter_staged(chunks, dev)
                 return
             for chunk in chunks:
                 self._validate_refs(chunk)
+            if usp is not None:
+                yield from self._iter_usp(chunks, dev, usp)
+                return
             ing = self._ingest
             if ing is None or ing.B != self.batch_size or ing.max_len != max_len or ing.device != dev:
                 ing = self._ingest = HiddenStateIngest([], batch_size=self.batch_size, max_len=max_len, device=dev)
@@ -359,6 +419,18 @@ def uninstall() -> None:
 uninstall_backend = uninstall
 
 
+def _draft_config_dict(cfg) -> Optional[dict]:
+    """the draft-config JSON the run YAML names (``model.draft_model_config``), or None when it is not a readable file"""
+    import json
+    import os
+
+    path = getattr(getattr(cfg, "model", None), "draft_model_config", None)
+    if not isinstance(path, str) or not os.path.isfile(path):
+        return None
+    with open(path) as f:
+        return json.load(f)
+
+
 def main(argv=None, *, worker_prefix=None) -> int:
     """``python -m specforge_amd.reference_plugin train -c run.yaml [--role ...] [--node-rank N] [--plan] [overrides ...]`` --
     ``specforge train`` (cli.py:167-268) on the HIP path with the SAME run YAML / draft JSON: the reference's own ``load_config``,
@@ -392,6 +464,7 @@ def main(argv=None, *, worker_prefix=None) -> int:
 
     install(override=True)
     cfg = load_config(args.config, args.overrides)
+    check_training_topology(cfg.training, _draft_config_dict(cfg), mode=cfg.mode)    # before any process group or engine exists
     resolved = resolve_run(cfg, registry=registry(override=True))
     me = tuple(worker_prefix) if worker_prefix else (sys.executable, "-m", "specforge_amd.reference_plugin")
     plan = build_launch_plan(resolved.config, algorithm=resolved.algorithm, config_path=args.config, overrides=args.overrides,

@@ -248,6 +248,38 @@ def make_usp_groups(sp_size: int, sp_ring_size: int = 1):
     return sp_group, uly_group, ring_group, dp_group
 
 
+def adopt_usp_groups(pc):
+    """(sp_group, ulysses_group, ring_group, draft_dp_group) of this rank taken from a ``ParallelConfig`` that already carries the groups
+    ``specforge.distributed.init_distributed`` built (the reference's ``ParallelConfig.from_distributed``, training/backend.py:64-123:
+    ``draft_sp_group``, ``sp_ulysses_group``, ``sp_ring_group``, ``draft_dp_group``), in ``make_usp_groups``' form -- ulysses_group is
+    the SP group when the ring degree is 1 and None for a pure ring, ring_group None when the ring degree is 1.  No group is created.
+    Refuses groups whose sizes disagree with the configured degrees, or whose ranks break the engine's convention sp_rank = ring_rank * u +
+    ulysses_rank (the engine's shards and ring offsets rest on it)."""
+    sp, r = int(pc.sp_size), int(getattr(pc, "sp_ring_size", 1) or 1)
+    u = sp // r
+    sp_group, uly, ring, dp = pc.draft_sp_group, getattr(pc, "sp_ulysses_group", None), getattr(pc, "sp_ring_group", None), \
+        getattr(pc, "draft_dp_group", None)
+    size = lambda g: dist.get_world_size(g) if g is not None else 1
+    if size(sp_group) != sp or (u > 1 and size(uly) != u) or (r > 1 and size(ring) != r) or dp is None \
+            or size(dp) * sp != dist.get_world_size():
+        raise ValueError(f"the process groups handed to the backend do not match sp_ulysses_size {u} x sp_ring_size {r}: draft_sp_group "
+                         f"has {size(sp_group)} ranks, sp_ulysses_group {size(uly)}, sp_ring_group {size(ring)}, draft_dp_group "
+                         f"{size(dp) if dp is not None else None} (world {dist.get_world_size()})")
+    members = dist.get_process_group_ranks(sp_group)
+    me = dist.get_rank()
+    uly_rank = dist.get_rank(uly) if u > 1 else 0
+    ring_rank = dist.get_rank(ring) if r > 1 else 0
+    sp_rank = dist.get_rank(sp_group)
+    inside = all(x in members for g in ((uly,) if u > 1 else ()) + ((ring,) if r > 1 else ()) for x in dist.get_process_group_ranks(g))
+    if not inside or sp_rank != ring_rank * u + uly_rank or members[sp_rank] != me:
+        raise ValueError(f"rank {me}: the adopted groups break the USP rank convention sp_rank = ring_rank * sp_ulysses_size + "
+                         f"ulysses_rank (draft_sp_group rank {sp_rank}, ring rank {ring_rank}, ulysses rank {uly_rank}, u = {u}; Ulysses "
+                         "peers must be consecutive inside the SP group, as yunchang's set_seq_parallel_pg(use_ulysses_low=True) lays them)")
+    if r == 1:
+        return sp_group, sp_group, None, dp
+    return sp_group, (uly if u > 1 else None), ring, dp
+
+
 class HipDPTrainingBackend:
     name = "hip_dp"
 
@@ -276,7 +308,11 @@ class HipDPTrainingBackend:
             raise ValueError(f"tp_size {self.parallel_config.tp_size}: tensor parallelism is not implemented by the HIP path")
         self.sp_ring_size = int(getattr(self.parallel_config, "sp_ring_size", 1) or 1)
         self.sp_group = self.draft_dp_group = self.sp_ulysses_group = self.sp_ring_group = None
-        if self.sp_ring_size > 1:       # ring (x Ulysses): the SP group split into its Ulysses and ring subgroups
+        if self.sp_size > 1 and getattr(self.parallel_config, "draft_sp_group", None) is not None:
+            # ``specforge train``: the reference built every group already (init_distributed) and its own code in this process keeps
+            # reading them (the USP transform, the evaluator, metric reduction): adopt them, build none
+            self.sp_group, self.sp_ulysses_group, self.sp_ring_group, self.draft_dp_group = adopt_usp_groups(self.parallel_config)
+        elif self.sp_ring_size > 1:       # ring (x Ulysses): the SP group split into its Ulysses and ring subgroups
             self.sp_group, self.sp_ulysses_group, self.sp_ring_group, self.draft_dp_group = make_usp_groups(self.sp_size, self.sp_ring_size)
         elif self.sp_size > 1:
             self.sp_group, self.draft_dp_group = make_sp_groups(self.sp_size)
