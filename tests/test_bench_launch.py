@@ -45,7 +45,7 @@ def _check_line(line, *, world, B, S, steps):
 
 def test_bare_gpus2_self_launch_two_ranks_over_gloo():
     line = _run([sys.executable, "bench.py", "--gpus", "2", "--small", "--batch", "2", "--seq", "512", "--dist-backend", "gloo",
-                 "--share-gpu", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"])
+                 "--share-gpu", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full"])
     _check_line(line, world=2, B=2, S=512, steps=2)
     r = line["rccl"]
     assert r["rccl_ranks"] == 2 and r["backend"] == "gloo" and not r["single_collective"]
@@ -59,7 +59,7 @@ def test_bare_gpus4_self_launch_four_ranks_over_gloo():
     takes no more than six).  The cold run must not die: one JSON line, all four ranks' tokens counted, the 7 gradient buckets
     all-reduced and their waits timed, per-rank spread reported (a straggler would show in the scaling record)."""
     line = _run([sys.executable, "bench.py", "--gpus", "4", "--small", "--batch", "1", "--seq", "256", "--dist-backend", "gloo",
-                 "--share-gpu", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], timeout=1500)
+                 "--share-gpu", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full"], timeout=1500)
     _check_line(line, world=4, B=1, S=256, steps=2)
     r = line["rccl"]
     assert r["rccl_ranks"] == 4 and r["backend"] == "gloo" and len(r["buckets"]) == 7
@@ -82,8 +82,8 @@ def test_four_concurrent_ingest_processes_smoke():
 
 def test_default_line_carries_the_configs_legs():
     """plumbing of the `configs` object (cfg 3 / 4 / 5 + the batch-1 recipe shape beside the headline): with --small dims every leg
-    runs the tiny model at its own (batch, seq); the real dims are what the default `python bench.py` line runs"""
-    line = _run([sys.executable, "bench.py", "--small", "--configs", "--config-steps", "2", "--steps", "2", "--warmup", "1", "--batch", "2",
+    runs the tiny model at its own (batch, seq); the real dims are what `python bench.py --full` runs"""
+    line = _run([sys.executable, "bench.py", "--full", "--small", "--configs", "--config-steps", "2", "--steps", "2", "--warmup", "1", "--batch", "2",
                  "--seq", "512", "--no-cpu-baseline", "--no-dense-mask", "--no-feeds"], timeout=1500)
     cf = line["configs"]
     sys.path.insert(0, ROOT)
@@ -105,6 +105,18 @@ def test_default_line_carries_the_configs_legs():
         assert abs(ms - cf[k]["ms_per_step"]) < 0.01 and abs(dfrac - cf[k]["draft_frac"]) < 1e-3 and isinstance(others, dict)
 
 
+def test_plain_line_runs_no_extra_legs():
+    """without --full a run is set-up, warm-up, the timed steps and the line (kernel timers included: they sit inside the timed
+    steps), none of the legs that take runs of their own; an option that adds such a leg is refused rather than ignored"""
+    line = _run([sys.executable, "bench.py", "--small", "--batch", "2", "--seq", "512", "--steps", "2", "--warmup", "1"])
+    _check_line(line, world=1, B=2, S=512, steps=2)
+    assert not {"dense_mask", "feeds", "sparse_loss_mask", "configs", "rccl", "cpu_baseline"} & set(line), sorted(line)
+    assert line["kernels"] and line["roofline"]["by_config"] is None
+    for opt in ("--dense-mask", "--feeds", "--configs"):
+        r = subprocess.run([sys.executable, "bench.py", opt], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+        assert r.returncode == 2 and "--full" in r.stderr, (opt, r.returncode, r.stderr[-1000:])
+
+
 def test_driver_command_line_torchrun_rccl_world1():
     import socket
 
@@ -113,7 +125,7 @@ def test_driver_command_line_torchrun_rccl_world1():
         port = sk.getsockname()[1]
     line = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                  "--master-port", str(port), "bench.py", "--gpus", "1", "--small", "--batch", "2", "--seq", "512", "--dist-backend", "nccl",
-                 "--force-dp", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-dense-mask", "--no-feeds"])
+                 "--force-dp", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-dense-mask", "--no-feeds", "--full"])
     _check_line(line, world=1, B=2, S=512, steps=2)
     r = line["rccl"]
     assert r["rccl_ranks"] == 1 and r["backend"] == "nccl" and len(r["buckets"]) >= 2
@@ -147,10 +159,10 @@ def test_dump_outputs_of_the_last_timed_step(tmp_path):
 
 
 def test_sparse_loss_mask_legs_and_option():
-    """the default line carries the sparse-loss-mask pair (loss-row compaction on / off) beside the headline; ``--loss-mask-density``
+    """the --full line carries the sparse-loss-mask pair (loss-row compaction on / off) beside the headline; ``--loss-mask-density``
     makes it the timed workload (labelled as not the headline), ``--no-compact`` its dense form: same loss up to bf16 summation order"""
     line = _run([sys.executable, "bench.py", "--small", "--batch", "2", "--seq", "512", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-                 "--no-dense-mask"])
+                 "--no-dense-mask", "--full"])
     sp = line["sparse_loss_mask"]
     assert 0.3 < sp["loss_mask_density"] < 0.7 and sp["compact"]["ms_per_step"] > 0 and sp["dense"]["ms_per_step"] > 0
     runs = []
@@ -165,7 +177,7 @@ def test_sparse_loss_mask_legs_and_option():
 
 def test_feed_table_and_ingest_fed_timed_region():
     line = _run([sys.executable, "bench.py", "--small", "--batch", "2", "--seq", "512", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
-                 "--no-dense-mask", "--feed", "ingest"])
+                 "--no-dense-mask", "--feed", "ingest", "--full"])
     _check_line(line, world=1, B=2, S=512, steps=3)
     assert line["feed"] == "ingest"
     f = line["feeds"]

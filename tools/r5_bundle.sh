@@ -1,5 +1,5 @@
 #!/bin/bash
-# round 5: the ONE measurement bundle of the round (usage: bash tools/r5_bundle.sh <commit>), taken last: full GPU suite (serial, the driver's command line), the default bench line
+# round 5: the ONE measurement bundle of the round (usage: bash tools/r5_bundle.sh <commit>), taken last: full GPU suite (serial, the driver's command line), the --full bench line
 # (feeds, dense mask, sparse mask, configs legs, CPU baseline), rocprofv3 kernel stats of the same command, PMC passes (one counter group per
 # run), per-shape GEMM table, attention A/B at head_dim 128 and 256, smoke.  Every command under its own `timeout`.
 export TMPDIR=/tmp

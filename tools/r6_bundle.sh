@@ -1,6 +1,6 @@
 #!/bin/bash
 # round 6: the ONE measurement bundle of the round (usage: bash tools/r6_bundle.sh <commit>), taken last: full GPU suite (serial, the driver's
-# command line), the default bench line under the driver's own arguments (feeds, dense mask, sparse mask, configs legs, CPU baseline,
+# command line), the --full bench line under the driver's own arguments (feeds, dense mask, sparse mask, configs legs, CPU baseline,
 # roofline.by_kernel / by_config), rocprofv3 kernel stats of the same command, PMC passes (one counter group per run), per-shape GEMM table,
 # attention bench, the DP telemetry of the RCCL world-1 path (per-bucket gradient-complete -> all-reduce-finished), smoke, short fuzz / soak.
 # Every command under its own `timeout`.
@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 C=${1:-unknown}
 O=gpurun_out/final; mkdir -p $O
 timeout 1500 python -m pytest tests/ -x -q -m gpu > $O/r6_gputests.log 2>&1; echo "gpu tests rc=$?"; tail -n 3 $O/r6_gputests.log
-timeout 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/r6_bench_stdout.log 2>$O/r6_bench_stderr.log; tail -1 $O/r6_bench_stdout.log > $O/r6_bench_line.json; echo "bench rc=$?"
+timeout 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/r6_bench_stdout.log 2>$O/r6_bench_stderr.log; tail -1 $O/r6_bench_stdout.log > $O/r6_bench_line.json; echo "bench rc=$?"
 rm -rf /tmp/prof; timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-dense-mask --no-feeds --no-configs > $O/prof_bench.log 2>&1
 cp $(find /tmp/prof -name "*kernel_stats.csv" | head -1) $O/r6_bench_kernel_stats.csv
 python tools/summarize_stats.py /tmp/prof > $O/r6_bench_kernel_stats_summary.txt 2>&1
@@ -20,9 +20,9 @@ timeout 120 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')
 bash tools/final_pmc.sh r6 $C; echo "pmc rc=$?"
 # DP telemetry on the only RCCL world a 1-GPU box has (world 1, forced collectives), default order and --dp-early-lm-head
 P=$(python -c "import socket; s=socket.socket(); s.bind(('127.0.0.1',0)); print(s.getsockname()[1])")
-timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port $P bench.py --gpus 1 --dist-backend nccl --force-dp --steps 6 --warmup 2 --no-cpu-baseline --no-dense-mask --no-feeds --no-configs 2>/dev/null | tail -1 > $O/r6_bench_rccl_world1_force_dp.json
+timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port $P bench.py --gpus 1 --dist-backend nccl --force-dp --full --steps 6 --warmup 2 --no-cpu-baseline --no-dense-mask --no-feeds --no-configs 2>/dev/null | tail -1 > $O/r6_bench_rccl_world1_force_dp.json
 P=$(python -c "import socket; s=socket.socket(); s.bind(('127.0.0.1',0)); print(s.getsockname()[1])")
-timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port $P bench.py --gpus 1 --dist-backend nccl --force-dp --dp-early-lm-head --steps 6 --warmup 2 --no-cpu-baseline --no-dense-mask --no-feeds --no-configs 2>/dev/null | tail -1 > $O/r6_bench_rccl_world1_force_dp_early_lm_head.json
+timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port $P bench.py --gpus 1 --dist-backend nccl --force-dp --dp-early-lm-head --full --steps 6 --warmup 2 --no-cpu-baseline --no-dense-mask --no-feeds --no-configs 2>/dev/null | tail -1 > $O/r6_bench_rccl_world1_force_dp_early_lm_head.json
 timeout 200 python tools/engine_fuzz.py --cases 150 --seed 11 > $O/r6_fuzz_engine_final.jsonl 2>/dev/null; echo "engine fuzz rc=$?"
 timeout 100 python tools/kernel_fuzz.py --cases 300 --seed 11 > $O/r6_fuzz_kernel_final.jsonl 2>/dev/null; echo "kernel fuzz rc=$?"
 timeout 150 python tools/soak.py --steps 400 --seed 11 > $O/r6_soak_final.jsonl 2>/dev/null; echo "soak rc=$?"
