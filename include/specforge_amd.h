@@ -112,6 +112,15 @@ int sf_ce_fused_zt(void* logits, int dtype, long ld, int rows, int V, const void
                    const long long* tgt_ids_pad, const float* pod_scale_pad, const float* tsum_pad, const long long* d2t,
                    float grad_scale, int write_grad, float* row_loss, float* row_correct, float* row_accept, int* row_pred, const long long* row_map,
                    void* stream);
+/* sf_ce_fused_zt with St teacher rows per sample (S <= St <= Spad): zt is [B*St, ldzt], row r = b*S+s of TTT step `off` reads
+ * zt[b*St+s+off] and zmd_pad / zinv_pad / the masks at padded index b*Spad+s+off, and only positions s+off >= St are forced to position
+ * mask 0.  Under sequence parallelism (USP) a rank's teacher covers its chunk plus the T rows of overlap from the next shard -- real
+ * targets, not constant tails -- so St = S+T.  With St == S the results are bit-identical to sf_ce_fused_zt. */
+int sf_ce_fused_zt_rows(void* logits, int dtype, long ld, int rows, int V, const void* zt, long ldzt, const float* zmd_pad,
+                        const float* zinv_pad, int S, int St, int Spad, int off, const int* pos_mask_pad, const int* loss_mask_pad,
+                        const long long* tgt_ids_pad, const float* pod_scale_pad, const float* tsum_pad, const long long* d2t,
+                        float grad_scale, int write_grad, float* row_loss, float* row_correct, float* row_accept, int* row_pred,
+                        const long long* row_map, void* stream);
 int sf_ce_lk_grad(void* logits, int dtype, long ld, int rows, int V, const float* target, int S, int Spad, int off,
                   const int* pos_mask_pad, const float* pod_scale_pad, const float* tsum_pad, int lk_mode,
                   float kl_scale, float kl_decay, float step_scale, float kl_row_scale, const float* accept_sum,

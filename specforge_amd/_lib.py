@@ -40,6 +40,8 @@ _SIGS = {
     "sf_gemm_nt_teacher_reduces": (c_int, [c_int, c_int, c_int, c_int]),
     "sf_ce_fused_zt": (c_int, [P, c_int, c_long, c_int, c_int, P, c_long, P, P, c_int, c_int, c_int, P, P, P, P, P, P, c_float, c_int, P, P,
                                P, P, P, P]),
+    "sf_ce_fused_zt_rows": (c_int, [P, c_int, c_long, c_int, c_int, P, c_long, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, c_float,
+                                    c_int, P, P, P, P, P, P]),
     "sf_rmsnorm_fwd": (c_int, [P, c_int, c_long, P, c_int, c_int, c_int, P, c_float, c_int, c_int, P, c_long, P, P]),
     "sf_rmsnorm_fwd2": (c_int, [P, c_int, c_long, P, P, c_long, P, P, P, c_long, P, c_float, c_int, c_int, P]),
     "sf_rmsnorm_bwd2": (c_int, [P, c_long, P, P, c_int, P, c_long, P, P, c_int, c_int, P, c_long, P, c_int, c_int, P, c_long, P, c_long, P, P]),

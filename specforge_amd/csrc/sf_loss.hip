@@ -48,7 +48,8 @@ SF_DEVICE void md_merge(float& m, float& d, float m2, float d2) {
 // target_p[:, idx:idx+S] and shifts ids/masks left with zero fill -- zero-padded tails
 // make the shift an offset).
 // ZT = 1: the soft target is not read as fp32 probabilities but formed on the fly from the teacher's stored draft logits,
-// p_j = exp(zt[row'][j] - zmd) * zinv with row' = b*S + s + off (NATURAL rows: a row with a position mask has s + off < S) and
+// p_j = exp(zt[row'][j] - zmd) * zinv with row' = b*St + s + off (St teacher rows per sample: St = S without sequence parallelism --
+// a row with a position mask has s + off < S --, S + T under USP, whose last T teacher rows are the next shard's first positions) and
 // (zmd, zinv) = the row's draft maximum and 1 / sum-exp from sf_teacher_reduce_perm -- the expression that kernel uses when it
 // writes target_p, so both forms give the same bits; 2 bytes per element instead of 4, and [B, S, Vd] fp32 is never written.
 template <typename T, int ZT = 0>
@@ -58,7 +59,7 @@ ce_fused_kernel(T* logits, long ld, int V, const float* target, int S, int Spad,
                 const float* pod_scale_pad, const float* tsum_pad, const long long* d2t, float grad_scale,
                 int write_grad, float* row_loss, float* row_correct, float* row_accept, int* row_pred,
                 const sf_bf16* zt = nullptr, long ldzt = 0, const float* zmd_pad = nullptr, const float* zinv_pad = nullptr,
-                const long long* row_map = nullptr) {
+                const long long* row_map = nullptr, int St = 0) {
     SF_SHARED float red[32];
     SF_SHARED int redi[16];
     const int r = (int)blockIdx.x;
@@ -131,12 +132,12 @@ ce_fused_kernel(T* logits, long ld, int V, const float* target, int S, int Spad,
         am = am_pick(am, ArgMax{red[16 + i], redi[i]});
     }
     const float lse = m + sf_log(d);
-    const int pm = (ZT && s + off >= S) ? 0 : pos_mask_pad[pr];     // (ZT: padded positions have no teacher row; their mask is 0 anyway)
+    const int pm = (ZT && s + off >= St) ? 0 : pos_mask_pad[pr];    // (ZT: padded positions have no teacher row; their mask is 0 anyway)
 
     float loss = 0.f, acc_min = 0.f;
     if (pm != 0) {
         const float* tp = ZT ? nullptr : target + pr * (long)V;
-        const sf_bf16* zr = ZT ? zt + ((long)b * S + s + off) * ldzt : nullptr;
+        const sf_bf16* zr = ZT ? zt + ((long)b * St + s + off) * ldzt : nullptr;
         const float zmd = ZT ? zmd_pad[pr] : 0.f, zinv = ZT ? zinv_pad[pr] : 0.f;
         const float podc = pod_scale_pad ? pod_scale_pad[pr] : 0.f;
         float tsum;
@@ -755,23 +756,46 @@ extern "C" int sf_eagle3_metrics(const float* met, const int* loss_mask_pad, con
     return sf_check_launch("sf_eagle3_metrics");
 }
 
+namespace {
+int ce_fused_zt_launch(const char* what, void* logits, int dtype, long ld, int rows, int V, const void* zt, long ldzt, const float* zmd_pad,
+                       const float* zinv_pad, int S, int St, int Spad, int off, const int* pos_mask_pad, const int* loss_mask_pad,
+                       const long long* tgt_ids_pad, const float* pod_scale_pad, const float* tsum_pad, const long long* d2t,
+                       float grad_scale, int write_grad, float* row_loss, float* row_correct, float* row_accept, int* row_pred,
+                       const long long* row_map, void* stream) {
+    SF_CHECK_ARG(rows >= 0 && V > 0 && S > 0 && St >= S && Spad >= St && off >= 0 && off + S <= Spad && (row_map || rows % S == 0), what);
+    SF_CHECK_ARG(dtype == SF_BF16 || dtype == SF_F32, what);
+    SF_CHECK_ARG(ld % 8 == 0 && V % 8 == 0 && ldzt % 8 == 0 && ldzt >= V, what);
+    SF_CHECK_ARG(zt && zmd_pad && zinv_pad && tsum_pad && pos_mask_pad, what);
+    if (rows == 0) return 0;
+    if (dtype == SF_BF16)
+        SF_LAUNCH((ce_fused_kernel<sf_bf16, 1>), dim3(rows), dim3(256), 0, stream, (sf_bf16*)logits, ld, V, (const float*)nullptr, S, Spad,
+                  off, pos_mask_pad, loss_mask_pad, tgt_ids_pad, pod_scale_pad, tsum_pad, d2t, grad_scale, write_grad,
+                  row_loss, row_correct, row_accept, row_pred, (const sf_bf16*)zt, ldzt, zmd_pad, zinv_pad, row_map, St);
+    else
+        SF_LAUNCH((ce_fused_kernel<float, 1>), dim3(rows), dim3(256), 0, stream, (float*)logits, ld, V, (const float*)nullptr, S, Spad,
+                  off, pos_mask_pad, loss_mask_pad, tgt_ids_pad, pod_scale_pad, tsum_pad, d2t, grad_scale, write_grad,
+                  row_loss, row_correct, row_accept, row_pred, (const sf_bf16*)zt, ldzt, zmd_pad, zinv_pad, row_map, St);
+    return sf_check_launch(what);
+}
+}  // namespace
+
 extern "C" int sf_ce_fused_zt(void* logits, int dtype, long ld, int rows, int V, const void* zt, long ldzt, const float* zmd_pad,
                               const float* zinv_pad, int S, int Spad, int off, const int* pos_mask_pad, const int* loss_mask_pad,
                               const long long* tgt_ids_pad, const float* pod_scale_pad, const float* tsum_pad, const long long* d2t,
                               float grad_scale, int write_grad, float* row_loss, float* row_correct, float* row_accept, int* row_pred,
                               const long long* row_map, void* stream) {
-    SF_CHECK_ARG(rows >= 0 && V > 0 && S > 0 && Spad >= S && off >= 0 && off + S <= Spad && (row_map || rows % S == 0), "sf_ce_fused_zt: bad shape");
-    SF_CHECK_ARG(dtype == SF_BF16 || dtype == SF_F32, "sf_ce_fused_zt: dtype");
-    SF_CHECK_ARG(ld % 8 == 0 && V % 8 == 0 && ldzt % 8 == 0 && ldzt >= V, "sf_ce_fused_zt: ld, ldzt and V must be multiples of 8");
-    SF_CHECK_ARG(zt && zmd_pad && zinv_pad && tsum_pad && pos_mask_pad, "sf_ce_fused_zt: teacher logits, their row scalars and tsum are required");
-    if (rows == 0) return 0;
-    if (dtype == SF_BF16)
-        SF_LAUNCH((ce_fused_kernel<sf_bf16, 1>), dim3(rows), dim3(256), 0, stream, (sf_bf16*)logits, ld, V, (const float*)nullptr, S, Spad,
-                  off, pos_mask_pad, loss_mask_pad, tgt_ids_pad, pod_scale_pad, tsum_pad, d2t, grad_scale, write_grad,
-                  row_loss, row_correct, row_accept, row_pred, (const sf_bf16*)zt, ldzt, zmd_pad, zinv_pad, row_map);
-    else
-        SF_LAUNCH((ce_fused_kernel<float, 1>), dim3(rows), dim3(256), 0, stream, (float*)logits, ld, V, (const float*)nullptr, S, Spad,
-                  off, pos_mask_pad, loss_mask_pad, tgt_ids_pad, pod_scale_pad, tsum_pad, d2t, grad_scale, write_grad,
-                  row_loss, row_correct, row_accept, row_pred, (const sf_bf16*)zt, ldzt, zmd_pad, zinv_pad, row_map);
-    return sf_check_launch("sf_ce_fused_zt");
+    return ce_fused_zt_launch("sf_ce_fused_zt: bad arguments", logits, dtype, ld, rows, V, zt, ldzt, zmd_pad, zinv_pad, S, S, Spad, off,
+                              pos_mask_pad, loss_mask_pad, tgt_ids_pad, pod_scale_pad, tsum_pad, d2t, grad_scale, write_grad, row_loss,
+                              row_correct, row_accept, row_pred, row_map, stream);
+}
+
+// St teacher rows per sample (S <= St <= Spad): the USP form, whose teacher covers the chunk plus the T rows of overlap
+extern "C" int sf_ce_fused_zt_rows(void* logits, int dtype, long ld, int rows, int V, const void* zt, long ldzt, const float* zmd_pad,
+                                   const float* zinv_pad, int S, int St, int Spad, int off, const int* pos_mask_pad, const int* loss_mask_pad,
+                                   const long long* tgt_ids_pad, const float* pod_scale_pad, const float* tsum_pad, const long long* d2t,
+                                   float grad_scale, int write_grad, float* row_loss, float* row_correct, float* row_accept, int* row_pred,
+                                   const long long* row_map, void* stream) {
+    return ce_fused_zt_launch("sf_ce_fused_zt_rows: bad arguments", logits, dtype, ld, rows, V, zt, ldzt, zmd_pad, zinv_pad, S, St, Spad,
+                              off, pos_mask_pad, loss_mask_pad, tgt_ids_pad, pod_scale_pad, tsum_pad, d2t, grad_scale, write_grad, row_loss,
+                              row_correct, row_accept, row_pred, row_map, stream);
 }

@@ -30,6 +30,21 @@ def loss_mask_suffix_counts(loss_mask: torch.Tensor, n: int = ops.MAX_DIAG + 1):
     return [int(col[k]) if k < len(col) else 0 for k in range(n)]
 
 
+def loss_mask_window_counts(loss_mask: torch.Tensor, ttt_length: int):
+    """The USP form of ``loss_mask_suffix_counts``: a rank's [B, S + T] loss mask covers its chunk of S rows plus the T rows of overlap
+    from the next shard, and TTT step k scores chunk row s against the mask at s + k -- which may lie in the overlap.  -> [count of
+    (b, s), s in [0, S), with loss_mask[b, s + k] != 0 for k in range(T)] as python ints (window sums, not suffix sums), from a HOST
+    copy of the mask (the ingest's pinned slot, a CPU batch): never a device read-back."""
+    assert not loss_mask.is_cuda
+    T = int(ttt_length)
+    col = (loss_mask.reshape(loss_mask.shape[0], -1) != 0).sum(dim=0)
+    S = col.numel() - T
+    if S <= 0:
+        return [0] * T
+    cs = torch.nn.functional.pad(col.cumsum(0), (1, 0)).tolist()
+    return [int(cs[k + S] - cs[k]) for k in range(T)]
+
+
 def padding_left_shift(t: torch.Tensor) -> torch.Tensor:
     """``padding(tensor, left=False)`` (specforge/utils.py:128-135): shift left by one along dim 1, zero fill."""
     return torch.cat((t[:, 1:], torch.zeros_like(t[:, -1:])), dim=1)
@@ -265,11 +280,17 @@ class Eagle3TrainStrategy:
         if self.eagle3_model.attention_backend == "usp":
             tensors = usp_unpad(tensors)
         # rows per TTT step that carry a loss (host integers): from the loader's metadata, or from the mask while it is still a CPU tensor
+        # (USP: per-rank window counts over the chunk + T rows of overlap, loss_mask_window_counts)
         md = getattr(batch, "metadata", None) or {}
-        counts = md.get("loss_mask_suffix_counts")
         lm0 = tensors.get("loss_mask")
-        if counts is None and lm0 is not None and not lm0.is_cuda:
-            counts = loss_mask_suffix_counts(lm0)
+        if self.eagle3_model.attention_backend == "usp":
+            counts = md.get("loss_mask_window_counts", getattr(batch, "loss_mask_window_counts", None))
+            if counts is None and lm0 is not None and not lm0.is_cuda:
+                counts = loss_mask_window_counts(lm0, self.eagle3_model.length)
+        else:
+            counts = md.get("loss_mask_suffix_counts")
+            if counts is None and lm0 is not None and not lm0.is_cuda:
+                counts = loss_mask_suffix_counts(lm0)
         pid0 = tensors.get("position_ids")
         span = (int(pid0.min()), int(pid0.max())) if pid0 is not None and not pid0.is_cuda and pid0.numel() else None
         t = self._resident(tensors)

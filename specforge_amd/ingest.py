@@ -34,7 +34,7 @@ from typing import Dict, Iterator, List, Optional, Sequence
 
 import torch
 
-from .eagle3 import TrainBatch, loss_mask_suffix_counts
+from .eagle3 import TrainBatch, loss_mask_suffix_counts, loss_mask_window_counts
 from .training import distributed_sampler_indices
 
 
@@ -448,15 +448,16 @@ class HiddenStateIngest:
                     slot = self._slots[si]
                     if slot.released is not None:      # the consumer's stream must be past this slot's tensors
                         slot.released.synchronize()
-                    if self.sp_size > 1:    # this rank's shard, read as such (the engine's USP mode takes no suffix counts)
-                        L, counts = self._fill_shard(slot, g[0]), None
+                    if self.sp_size > 1:    # this rank's shard, read as such; window counts over the chunk + ttt_length rows the engine takes
+                        L = self._fill_shard(slot, g[0])
+                        counts = loss_mask_window_counts(slot.h["loss_mask"][:1, :L["hidden_state"]], self.ttt_length)
                     else:
                         L = self._fill(slot, g)
                         counts = loss_mask_suffix_counts(slot.h["loss_mask"][:len(g), :L])   # (host side: the engine's loss-row compaction)
                     if self._copy_stream is not None:
                         with torch.cuda.stream(self._copy_stream):
                             for k in slot.h:
-                                Lk = L[k] if counts is None else L
+                                Lk = L[k] if isinstance(L, dict) else L
                                 slot.dview(k, Lk)[:len(g)].copy_(slot.h[k][:len(g), :Lk], non_blocking=True)
                             slot.copied = torch.cuda.Event()
                             slot.copied.record()
@@ -486,12 +487,12 @@ class HiddenStateIngest:
                 nb = len(g)
                 if self._copy_stream is not None:
                     torch.cuda.current_stream().wait_event(slot.copied)
-                if counts is None:          # a USP shard: per-tensor lengths
+                if isinstance(L, dict):     # a USP shard: per-tensor lengths
                     if self._copy_stream is not None:
                         tensors = {k: slot.dview(k, L[k])[:nb] for k in slot.d}
                     else:
                         tensors = {k: v[:nb, :L[k]].clone() for k, v in slot.h.items()}
-                    md = {"target_repr": "hidden_state", "sample_files": list(g)}
+                    md = {"target_repr": "hidden_state", "sample_files": list(g), "loss_mask_window_counts": counts}
                 else:
                     if self._copy_stream is not None:
                         tensors = {k: slot.dview(k, L)[:nb] for k in slot.d}

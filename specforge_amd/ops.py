@@ -135,6 +135,22 @@ def ce_fused_zt(logits: torch.Tensor, zt: torch.Tensor, zmd_pad: torch.Tensor, z
                                 _p(row_map), _stream()), "sf_ce_fused_zt")
 
 
+def ce_fused_zt_rows(logits: torch.Tensor, zt: torch.Tensor, zmd_pad: torch.Tensor, zinv_pad: torch.Tensor, *, S: int, St: int, Spad: int,
+                     off: int, pos_mask_pad, loss_mask_pad, tgt_ids_pad=None, pod_scale_pad=None, tsum_pad, d2t=None, grad_scale: float = 1.0,
+                     write_grad: bool = True, row_loss, row_correct, row_accept, row_pred=None, row_map=None):
+    """ce_fused_zt with ``St`` teacher rows per sample (``zt`` [B*St, >= V]; USP: the chunk + the T rows of overlap); row (b, s) of step
+    ``off`` reads zt[b*St + s + off]"""
+    L = _lib.lib()
+    rows, V = logits.shape
+    assert zt.dtype == torch.bfloat16 and zt.shape[1] >= V and (row_map is not None or zt.shape[0] >= rows // S * St)
+    assert row_map is None or (row_map.dtype == torch.int64 and row_map.numel() >= rows and row_map.is_contiguous())
+    assert zmd_pad.dtype == zinv_pad.dtype == torch.float32 and zmd_pad.is_contiguous() and zinv_pad.is_contiguous()
+    _lib.check(L.sf_ce_fused_zt_rows(_p(logits), _dt(logits), _rowmajor(logits), rows, V, _p(zt), _rowmajor(zt), _p(zmd_pad), _p(zinv_pad),
+                                     S, St, Spad, off, _p(pos_mask_pad), _p(loss_mask_pad), _p(tgt_ids_pad), _p(pod_scale_pad), _p(tsum_pad),
+                                     _p(d2t), grad_scale, 1 if write_grad else 0, _p(row_loss), _p(row_correct), _p(row_accept),
+                                     _p(row_pred), _p(row_map), _stream()), "sf_ce_fused_zt_rows")
+
+
 def ce_lk_grad(logits: torch.Tensor, target_pad: torch.Tensor, *, S: int, Spad: int, off: int, pos_mask_pad, pod_scale_pad,
                tsum_pad=None, lk_loss_type: str, kl_scale: float, kl_decay: float, step_scale: float, kl_row_scale: float,
                accept_sum: torch.Tensor, mask_sum: torch.Tensor):

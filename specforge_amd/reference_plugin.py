@@ -34,7 +34,7 @@ from typing import Any, Optional
 
 import torch
 
-from .eagle3 import Eagle3TrainStrategy, OnlineEagle3Model, loss_mask_suffix_counts
+from .eagle3 import Eagle3TrainStrategy, OnlineEagle3Model, loss_mask_suffix_counts, loss_mask_window_counts, usp_unpad
 from .model import DraftConfig, Eagle3DraftMethods
 from .training import BF16Optimizer, HipDPTrainingBackend
 
@@ -224,6 +224,14 @@ def _device_for_batches() -> torch.device:
     return torch.device("cuda", torch.cuda.current_device())
 
 
+def _carry_window_counts(batch, counts) -> None:
+    """hand a USP batch's per-rank loss-row window counts (``eagle3.loss_mask_window_counts``) to ``Eagle3TrainStrategy.forward_loss``
+    as an attribute of the batch object, not a metadata key: the batch's fields stay exactly the reference's (its dataclass equality
+    ignores the attribute), and the trainer hands the same object to the strategy (training/controller.py:328-331)"""
+    if counts is not None:
+        batch.loss_mask_window_counts = counts
+
+
 def feature_loader_class():
     """``FeatureDataLoader`` (runtime/data_plane/feature_dataloader.py:92-320) with the refs-mode (offline) iteration on
     the HIP ingest.  Queue mode (online / streaming) is the reference's own code, untouched."""
@@ -295,9 +303,11 @@ def feature_loader_class():
                                                        ttt_length=ttt, collator_layout=True, sp_ulysses_size=u)
             groups = [[r.feature_store_uri[len("file://"):] for r in chunk] for chunk in chunks]
             for chunk, b in zip(chunks, ing.stream(groups)):
-                yield RefTrainBatch(sample_ids=[r.sample_id for r in chunk], strategy=self.strategy, tensors=b.tensors,
+                out = RefTrainBatch(sample_ids=[r.sample_id for r in chunk], strategy=self.strategy, tensors=b.tensors,
                                     metadata={"target_repr": chunk[0].metadata.get("target_repr"),
                                               "ttt_length": chunk[0].metadata.get("ttt_length")})
+                _carry_window_counts(out, b.metadata.get("loss_mask_window_counts"))
+                yield out
 
         def _iter_refs(self):
             skip, self._seek_batches = self._seek_batches, 0        # feature_dataloader.py:257-266
@@ -336,10 +346,14 @@ def feature_loader_class():
             pinned slot + copy stream instead of the strategy's pageable ``.to(device)``"""
             from concurrent.futures import ThreadPoolExecutor
 
+            usp = self._usp_plan()
+
             def counted(batch):
                 lm = batch.tensors.get("loss_mask")
                 if lm is not None and not lm.is_cuda and isinstance(batch.metadata, dict):
                     batch.metadata.setdefault("loss_mask_suffix_counts", loss_mask_suffix_counts(lm))
+                    if usp is not None:     # a USP shard: window counts over the rows the engine takes (chunk + ttt_length)
+                        _carry_window_counts(batch, loss_mask_window_counts(usp_unpad(batch.tensors)["loss_mask"], usp[1]))
                 return batch
 
             if dev.type != "cuda":

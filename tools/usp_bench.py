@@ -1,6 +1,7 @@
 """USP (attention_backend "usp") step and layout-kernel timing: one JSON line per run.
 
     python tools/usp_bench.py --sp 2 --seq 32768 [--ring R] [--config llama3-8b|cfg1|hd256] [--backend gloo|nccl] [--steps 3] [--warmup 1]
+                              [--loss-mask-density D]
 
 Starts ``--sp`` ranks (gloo: all on cuda:0, exchange staged through pinned host buffers -- a PLUMBING run, not a scaling number;
 nccl: rank r on cuda:r), each training the Llama-3-8B draft dims on its shard of one 1 x seq sample.  Reports ms / step and
@@ -12,7 +13,12 @@ their bytes (one read + one write of the image) reach.
 The line then reports per rank the ms / step, the exposed exchange time split into the Ulysses all-to-alls and the ring all-gather /
 reduce-scatter, and the query-offset attention kernels at that rank's shape (its u * chunk rows at offset ring_rank * u * chunk):
 µs per launch and the fraction of the 2.5 PFLOP/s MFMA peak, FLOPs from shapes as in tools/attn_bench.py (fwd 4, dQ 6, dK/dV 8 x
-nh/u * hd * (q_off * Sq + Sq^2 / 2)).  ``hd256``: the head_dim-256 draft of configs/qwen3-next-80b-a3b-eagle3.json (16 / 2 heads)."""
+nh/u * hd * (q_off * Sq + Sq^2 / 2)).  ``hd256``: the head_dim-256 draft of configs/qwen3-next-80b-a3b-eagle3.json (16 / 2 heads).
+
+``--loss-mask-density D``: the sample's loss mask is bench.py's (``make_loss_mask``: all ones at 1.0, chat-like turns below) and stays in
+host memory, so every rank hands its window counts (``eagle3.loss_mask_window_counts``) to the engine -- loss-row compaction and the
+gathered teacher below the 0.9 cut-off.  Without it the mask is tests/_usp_gpu.py's (density 0.5, device-resident: no host counts, the
+dense rows).  Every rank reports its peak allocation (``torch.cuda.max_memory_allocated``) over the run."""
 import argparse
 import json
 import os
@@ -125,6 +131,11 @@ def _rank(a):
     dist.init_process_group(a.backend, rank=a.rank, world_size=a.sp)
     pc = ParallelConfig(world_size=a.sp, sp_size=a.sp, sp_ring_size=a.ring, dp_size=1)
     eagle, strat, backend, batch = W.setup(a.config, a.seq, dev, "usp", dict(parallel_config=pc))
+    if a.loss_mask_density is not None:
+        from bench import make_loss_mask
+
+        batch["loss_mask"] = make_loss_mask(1, a.seq, a.loss_mask_density, seed=5)     # host memory: the strategy takes the counts from it
+        batch["loss_mask"][0, -1] = 0
     shard = usp_shard(batch, ttt_length=T, sp_rank=a.rank, sp_size=a.sp)
     for _ in range(a.warmup):
         W.step(eagle, strat, backend, shard)
@@ -136,7 +147,9 @@ def _rank(a):
     eng = eagle.engine
     eng.sp_time_exchange, eng.sp_exchange_s, eng.sp_ring_exchange_s = True, 0.0, 0.0
     W.step(eagle, strat, backend, shard)
-    res = dict(ms_per_step=ms, exchange_ms_per_step=(eng.sp_exchange_s + eng.sp_ring_exchange_s) * 1e3)
+    res = dict(ms_per_step=ms, exchange_ms_per_step=(eng.sp_exchange_s + eng.sp_ring_exchange_s) * 1e3,
+               peak_mem_gb=torch.cuda.max_memory_allocated(dev) / 1e9, teacher_compacted=eng._teacher_compacted, soft_targets=eng._soft[0],
+               lm_head_rows_compact=eng._lm_compact_K is not None)
     u = a.sp // a.ring
     if a.ring > 1:
         chunk = a.seq // a.sp
@@ -161,6 +174,7 @@ def main():
     ap.add_argument("--backend", default="gloo", choices=["gloo", "nccl"])
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--loss-mask-density", type=float, default=None)
     ap.add_argument("--timeout", type=int, default=1200)
     ap.add_argument("--rank", type=int, default=None)
     ap.add_argument("--port", type=int, default=0)
@@ -179,7 +193,9 @@ def main():
     outs = [f"/tmp/usp_bench_{os.getpid()}_{r}.pt" for r in range(a.sp)]
     procs = [subprocess.Popen([sys.executable, os.path.abspath(__file__), "--rank", str(r), "--port", str(port), "--sp", str(a.sp),
                                "--seq", str(a.seq), "--ring", str(a.ring), "--config", a.config, "--backend", a.backend, "--steps", str(a.steps),
-                               "--warmup", str(a.warmup), "--out", outs[r]], cwd=ROOT) for r in range(a.sp)]
+                               "--warmup", str(a.warmup), "--out", outs[r]]
+                              + ([] if a.loss_mask_density is None else ["--loss-mask-density", str(a.loss_mask_density)]), cwd=ROOT)
+             for r in range(a.sp)]
     try:
         rcs = [p.wait(timeout=a.timeout) for p in procs]
     except subprocess.TimeoutExpired:
@@ -197,7 +213,10 @@ def main():
                 kind="plumbing (ranks share one device, host-staged gloo exchange)" if a.backend == "gloo" else "rccl",
                 steps=a.steps, ms_per_step=round(ms, 2), tokens_per_s=round(a.seq / ms * 1e3, 1),
                 exposed_exchange_ms_per_step=round(max(r["exchange_ms_per_step"] for r in res), 2),
-                layout_kernels=res[0].get("kernels"))
+                layout_kernels=res[0].get("kernels"), loss_mask_density=a.loss_mask_density,
+                per_rank=[dict(rank=x, ms_per_step=round(r["ms_per_step"], 2), peak_mem_gb=round(r["peak_mem_gb"], 3),
+                               teacher_compacted=r["teacher_compacted"], soft_targets=r["soft_targets"],
+                               lm_head_rows_compact=r["lm_head_rows_compact"]) for x, r in enumerate(res)])
     if a.ring > 1:
         line.update(ulysses=a.sp // a.ring, ring=a.ring, ranks=[
             dict(rank=x, ring_rank=r["ring_rank"], q_off=r["q_off"], ms_per_step=round(r["ms_per_step"], 2),
