@@ -125,6 +125,17 @@ int sf_ce_lk_grad(void* logits, int dtype, long ld, int rows, int V, const float
                   const int* pos_mask_pad, const float* pod_scale_pad, const float* tsum_pad, int lk_mode,
                   float kl_scale, float kl_decay, float step_scale, float kl_row_scale, const float* accept_sum,
                   const float* mask_sum, void* stream);
+/* sf_ce_lk_grad with the soft target given as the teacher's stored draft logits, addressed like sf_ce_fused_zt_rows: target_p[j] =
+ * exp(zt[b*St+s+off][j] - zmd) * zinv (the expression of sf_ce_fused_zt / sf_teacher_reduce_perm, so the p of this backward is the p the
+ * forward's acceptance sum saw); `rows` dense rows, or compact rows with row_map (row r of `logits` is token row row_map[r]; rows not
+ * listed are not written); positions s+off >= St count as position mask 0.  Same result definition as sf_ce_lk_grad: masked rows exactly
+ * zero, ties of torch.minimum split evenly.  tsum_pad and pod_scale_pad are required; ld / ldzt multiples of 8, V may have a tail
+ * (V % 8 != 0).  A row of up to 32 768 columns is read from memory once (it stays in registers for its three passes). */
+int sf_ce_lk_grad_zt_rows(void* logits, int dtype, long ld, int rows, int V, const void* zt, long ldzt, const float* zmd_pad,
+                          const float* zinv_pad, int S, int St, int Spad, int off, const int* pos_mask_pad,
+                          const float* pod_scale_pad, const float* tsum_pad, int lk_mode, float kl_scale, float kl_decay,
+                          float step_scale, float kl_row_scale, const float* accept_sum, const float* mask_sum,
+                          const long long* row_map, void* stream);
 
 /* out[i] = scale * sum(in[i*n : (i+1)*n]) in a fixed order (double accumulation): deterministic
  * replacement of the .sum()/.mean() reductions in eagle3/model.py:161-190. */

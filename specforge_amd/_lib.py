@@ -42,6 +42,8 @@ _SIGS = {
                                P, P, P, P]),
     "sf_ce_fused_zt_rows": (c_int, [P, c_int, c_long, c_int, c_int, P, c_long, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, c_float,
                                     c_int, P, P, P, P, P, P]),
+    "sf_ce_lk_grad_zt_rows": (c_int, [P, c_int, c_long, c_int, c_int, P, c_long, P, P, c_int, c_int, c_int, c_int, P, P, P, c_int, c_float,
+                                      c_float, c_float, c_float, P, P, P, P]),
     "sf_rmsnorm_fwd": (c_int, [P, c_int, c_long, P, c_int, c_int, c_int, P, c_float, c_int, c_int, P, c_long, P, P]),
     "sf_rmsnorm_fwd2": (c_int, [P, c_int, c_long, P, P, c_long, P, P, P, c_long, P, c_float, c_int, c_int, P]),
     "sf_rmsnorm_bwd2": (c_int, [P, c_long, P, P, c_int, P, c_long, P, P, c_int, c_int, P, c_long, P, c_int, c_int, P, c_long, P, c_long, P, P]),

@@ -294,6 +294,152 @@ ce_lk_grad_kernel(T* logits, long ld, int V, const float* target, int S, int Spa
     }
 }
 
+// The same gradient with the soft target re-formed from the teacher's stored draft logits, p_j = exp(zt[row'][j] - zmd) * zinv (the
+// expression of ce_fused_kernel<T, 1> and sf_teacher_reduce_perm: the p this backward compares with the draft softmax is the p the
+// forward's acceptance sum saw), on dense or compact (row_map) logits rows, St teacher rows per sample -- see ce_fused_kernel.
+// The row is needed three times (log-sum-exp; a_r and c_r, which need it; the gradient, which needs c_r) and its target twice.  Both
+// are loaded ONCE, as 16-byte chunks that stay in registers: LKZ_RC chunks of the logits and of zt per lane, all 2 * LKZ_RC loads
+// issued before the first use, and the launcher sizes the workgroup (up to 1024 lanes) so that a row of up to 1024 * LKZ_RC * 8 = 32 768
+// columns fits -- 16 + 16 VGPRs per lane for bf16 logits, no LDS copy (64 KB per bf16 row would leave two workgroups per CU) and
+// no second trip through L2.  Columns beyond that (larger draft vocabularies) are streamed again by each pass.  HBM traffic per
+// row with a position mask: logits read V * sizeof(T) + zt read 2 V + gradient written V * sizeof(T) (6 V bytes for bf16; sf_ce_lk_grad:
+// at least 2 V + 4 V + 2 V with three more logits reads and two more fp32 target reads left to the caches); a masked row: V * sizeof(T) written.
+constexpr int LKZ_RC = 4;
+template <typename T>
+SF_GLOBAL void SF_LAUNCH_BOUNDS(1024, 1)
+ce_lk_grad_zt_kernel(T* logits, long ld, int V, const sf_bf16* zt, long ldzt, const float* zmd_pad, const float* zinv_pad, int S, int St,
+                     int Spad, int off, const int* pos_mask_pad, const float* pod_scale_pad, const float* tsum_pad, int lk_mode,
+                     float kl_scale, float kl_decay, float step_scale, float kl_row_scale, const float* accept_sum,
+                     const float* mask_sum, const long long* row_map) {
+    SF_SHARED float red[32];
+    const int r = (int)blockIdx.x;
+    const int rt = row_map ? (int)row_map[r] : r;
+    const int b = rt / S, s = rt - b * S;
+    const long pr = (long)b * Spad + s + off;
+    T* x = logits + (long)r * ld;
+    const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
+    const int V8 = V >> 3;
+    const int pm = (s + off >= St) ? 0 : pos_mask_pad[pr];     // (positions past the teacher's rows have no target; their mask is 0 anyway)
+    if (pm == 0) {      // masked row: exactly zero (workgroup-uniform exit, before any barrier)
+        const float z8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        for (int c = tid; c < V8; c += nt) SfVec8<T>::st(x + c * 8, z8);
+        for (int j = V8 * 8 + tid; j < V; j += nt) SfElem<T>::st(x + j, 0.f);
+        return;
+    }
+    const sf_bf16* z = zt + ((long)b * St + s + off) * ldzt;
+    SfRaw8<T> xr[LKZ_RC];
+    SfRaw8<sf_bf16> zr[LKZ_RC];
+#pragma unroll
+    for (int u = 0; u < LKZ_RC; ++u)
+        if (tid + u * nt < V8) xr[u].ld(x + (tid + u * nt) * 8);
+#pragma unroll
+    for (int u = 0; u < LKZ_RC; ++u)
+        if (tid + u * nt < V8) zr[u].ld(z + (tid + u * nt) * 8);
+    const int c_over = tid + LKZ_RC * nt;       // this lane's first chunk beyond the register-resident ones
+    const float zmd = zmd_pad[pr], zinv = zinv_pad[pr], podc = pod_scale_pad[pr];
+
+    // pass 1: log-sum-exp (online max / sum-exp per lane, chunks folded in ascending order)
+    float m = SF_NEG_BIG, d = 0.f;
+    auto chunk1 = [&](const SfRaw8<T>& raw) {
+        float v[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = raw.at(i);
+        float cm = v[0];
+#pragma unroll
+        for (int i = 1; i < 8; ++i) cm = fmaxf(cm, v[i]);
+        const float mn = fmaxf(m, cm);
+        float acc = (m == SF_NEG_BIG) ? 0.f : d * sf_exp_fast(m - mn);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc += sf_exp_fast(v[i] - mn);
+        m = mn;
+        d = acc;
+    };
+#pragma unroll
+    for (int u = 0; u < LKZ_RC; ++u)
+        if (tid + u * nt < V8) chunk1(xr[u]);
+    for (int c = c_over; c < V8; c += nt) {
+        SfRaw8<T> raw;
+        raw.ld(x + c * 8);
+        chunk1(raw);
+    }
+    for (int j = V8 * 8 + tid; j < V; j += nt) md_merge(m, d, SfElem<T>::ld(x + j), 1.f);
+    for (int k = 32; k >= 1; k >>= 1) {
+        const float m2 = sf_shfl_xor(m, k), d2 = sf_shfl_xor(d, k);
+        md_merge(m, d, m2, d2);
+    }
+    const int w = tid >> 6, nw = nt >> 6;
+    if (sf_lane() == 0) { red[w] = m; red[16 + w] = d; }
+    sf_syncthreads();
+    m = red[0]; d = red[16];
+    for (int i = 1; i < nw; ++i) md_merge(m, d, red[i], red[16 + i]);
+    const float lse = m + sf_log(d);
+
+    // pass 2: a_r = sum min(q, s) and c_r = sum ind * s
+    float a = 0.f, cs = 0.f;
+    auto elem2 = [&](float xv, float zv) {
+        const float sm = sf_exp_fast(xv - lse), q = sf_exp_fast(zv - zmd) * zinv * podc;
+        a += fminf(q, sm);
+        cs += sm < q ? sm : (sm == q ? 0.5f * sm : 0.f);
+    };
+#pragma unroll
+    for (int u = 0; u < LKZ_RC; ++u)
+        if (tid + u * nt < V8) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) elem2(xr[u].at(i), zr[u].at(i));
+        }
+    for (int c = c_over; c < V8; c += nt) {
+        SfRaw8<T> raw;
+        SfRaw8<sf_bf16> zraw;
+        raw.ld(x + c * 8);
+        zraw.ld(z + c * 8);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) elem2(raw.at(i), zraw.at(i));
+    }
+    for (int j = V8 * 8 + tid; j < V; j += nt) elem2(SfElem<T>::ld(x + j), sf_bf2f(z[j]));
+    a = sf_block_sum(a, red);
+    cs = sf_block_sum(cs, red);
+    const float D = fmaxf(mask_sum[0], 1e-8f);
+    float ka, kb;  // g = ka * (s tsum - p) + kb * s (ind - c)
+    if (lk_mode == 1) {
+        ka = 0.f;
+        kb = a > 0.f ? -step_scale / (D * a) : 0.f;
+    } else {
+        const float alpha = accept_sum[0] / D;
+        const float wt = kl_scale * sf_exp(-kl_decay * alpha);
+        ka = step_scale * kl_row_scale * wt;
+        kb = -step_scale * (1.f - wt) / D;
+    }
+    const float tsum = tsum_pad[pr], pmf = (float)pm;
+    ka *= pmf;
+    kb *= pmf;
+
+    // pass 3: the gradient, in place
+    auto elem3 = [&](float xv, float zv) {
+        const float sm = sf_exp_fast(xv - lse), p = sf_exp_fast(zv - zmd) * zinv, q = p * podc;
+        const float ind = sm < q ? 1.f : (sm == q ? 0.5f : 0.f);
+        return ka * (sm * tsum - p) + kb * sm * (ind - cs);
+    };
+#pragma unroll
+    for (int u = 0; u < LKZ_RC; ++u)
+        if (tid + u * nt < V8) {
+            float g[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) g[i] = elem3(xr[u].at(i), zr[u].at(i));
+            SfVec8<T>::st(x + (tid + u * nt) * 8, g);
+        }
+    for (int c = c_over; c < V8; c += nt) {
+        SfRaw8<T> raw;
+        SfRaw8<sf_bf16> zraw;
+        raw.ld(x + c * 8);
+        zraw.ld(z + c * 8);
+        float g[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) g[i] = elem3(raw.at(i), zraw.at(i));
+        SfVec8<T>::st(x + c * 8, g);
+    }
+    for (int j = V8 * 8 + tid; j < V; j += nt) SfElem<T>::st(x + j, elem3(SfElem<T>::ld(x + j), sf_bf2f(z[j])));
+}
+
 // deterministic sum of n floats (fixed order, double accumulation): workgroup b sums segment b, out[b] = sum
 SF_GLOBAL void reduce_sum_kernel(const float* in_all, long n, float* out, float scale) {
     SF_SHARED double part[256];
@@ -697,6 +843,34 @@ extern "C" int sf_ce_lk_grad(void* logits, int dtype, long ld, int rows, int V, 
                   off, pos_mask_pad, pod_scale_pad, tsum_pad, lk_mode, kl_scale, kl_decay, step_scale, kl_row_scale,
                   accept_sum, mask_sum);
     return sf_check_launch("sf_ce_lk_grad");
+}
+
+extern "C" int sf_ce_lk_grad_zt_rows(void* logits, int dtype, long ld, int rows, int V, const void* zt, long ldzt, const float* zmd_pad,
+                                     const float* zinv_pad, int S, int St, int Spad, int off, const int* pos_mask_pad,
+                                     const float* pod_scale_pad, const float* tsum_pad, int lk_mode, float kl_scale, float kl_decay,
+                                     float step_scale, float kl_row_scale, const float* accept_sum, const float* mask_sum,
+                                     const long long* row_map, void* stream) {
+    SF_CHECK_ARG(rows >= 0 && V > 0 && S > 0 && St >= S && Spad >= St && off >= 0 && off + S <= Spad && (row_map || rows % S == 0),
+                 "sf_ce_lk_grad_zt_rows: bad shape");
+    SF_CHECK_ARG(dtype == SF_BF16 || dtype == SF_F32, "sf_ce_lk_grad_zt_rows: dtype");
+    SF_CHECK_ARG(lk_mode == 1 || lk_mode == 2, "sf_ce_lk_grad_zt_rows: lk_mode must be 1 (alpha) or 2 (lambda)");
+    SF_CHECK_ARG(ld % 8 == 0 && ld >= V && ldzt % 8 == 0 && ldzt >= V, "sf_ce_lk_grad_zt_rows: ld and ldzt must be multiples of 8 and >= V");
+    SF_CHECK_ARG(((size_t)logits & 15) == 0 && ((size_t)zt & 15) == 0, "sf_ce_lk_grad_zt_rows: logits and zt must be 16-byte aligned");
+    SF_CHECK_ARG(logits && zt && zmd_pad && zinv_pad && tsum_pad && pos_mask_pad && pod_scale_pad && accept_sum && mask_sum,
+                 "sf_ce_lk_grad_zt_rows: missing input");
+    if (rows == 0) return 0;
+    // lanes: enough for the whole row to stay in registers (LKZ_RC chunks of 8 per lane), between 4 and 16 waves
+    int nt = ((V / 8 + LKZ_RC - 1) / LKZ_RC + 63) / 64 * 64;
+    nt = nt < 256 ? 256 : (nt > 1024 ? 1024 : nt);
+    if (dtype == SF_BF16)
+        SF_LAUNCH((ce_lk_grad_zt_kernel<sf_bf16>), dim3(rows), dim3(nt), 0, stream, (sf_bf16*)logits, ld, V, (const sf_bf16*)zt, ldzt,
+                  zmd_pad, zinv_pad, S, St, Spad, off, pos_mask_pad, pod_scale_pad, tsum_pad, lk_mode, kl_scale, kl_decay, step_scale,
+                  kl_row_scale, accept_sum, mask_sum, row_map);
+    else
+        SF_LAUNCH((ce_lk_grad_zt_kernel<float>), dim3(rows), dim3(nt), 0, stream, (float*)logits, ld, V, (const sf_bf16*)zt, ldzt,
+                  zmd_pad, zinv_pad, S, St, Spad, off, pos_mask_pad, pod_scale_pad, tsum_pad, lk_mode, kl_scale, kl_decay, step_scale,
+                  kl_row_scale, accept_sum, mask_sum, row_map);
+    return sf_check_launch("sf_ce_lk_grad_zt_rows");
 }
 
 extern "C" int sf_reduce_sum(const float* in, long n, int nsegments, float* out, float scale, void* stream) {

@@ -165,6 +165,26 @@ def ce_lk_grad(logits: torch.Tensor, target_pad: torch.Tensor, *, S: int, Spad: 
                                kl_row_scale, _p(accept_sum), _p(mask_sum), _stream()), "sf_ce_lk_grad")
 
 
+def ce_lk_grad_zt(logits: torch.Tensor, zt: torch.Tensor, zmd_pad: torch.Tensor, zinv_pad: torch.Tensor, *, S: int, Spad: int, off: int,
+                  St: Optional[int] = None, pos_mask_pad, pod_scale_pad, tsum_pad, lk_loss_type: str, kl_scale: float, kl_decay: float,
+                  step_scale: float, kl_row_scale: float, accept_sum: torch.Tensor, mask_sum: torch.Tensor, row_map=None):
+    """ce_lk_grad with the soft target re-formed from the teacher's stored draft logits ``zt`` [B*St, >= V] and the per-row
+    (max, 1 / sum-exp) of teacher_reduce_perm; ``St`` teacher rows per sample (default S; USP: the chunk + the T rows of overlap);
+    ``row_map`` [rows] int64: logits row r is token row row_map[r] (loss-row compaction)"""
+    L = _lib.lib()
+    rows, V = logits.shape
+    St = S if St is None else St
+    mode = {"alpha": 1, "lambda": 2}[lk_loss_type]
+    assert zt.dtype == torch.bfloat16 and zt.shape[1] >= V and (row_map is not None or zt.shape[0] >= rows // S * St)
+    assert row_map is None or (row_map.dtype == torch.int64 and row_map.numel() >= rows and row_map.is_contiguous())
+    assert zmd_pad.dtype == zinv_pad.dtype == torch.float32 and zmd_pad.is_contiguous() and zinv_pad.is_contiguous()
+    assert accept_sum.dtype == torch.float32 and mask_sum.dtype == torch.float32
+    _lib.check(L.sf_ce_lk_grad_zt_rows(_p(logits), _dt(logits), _rowmajor(logits), rows, V, _p(zt), _rowmajor(zt), _p(zmd_pad), _p(zinv_pad),
+                                       S, St, Spad, off, _p(pos_mask_pad), _p(pod_scale_pad), _p(tsum_pad), mode, kl_scale, kl_decay,
+                                       step_scale, kl_row_scale, _p(accept_sum), _p(mask_sum), _p(row_map), _stream()),
+               "sf_ce_lk_grad_zt_rows")
+
+
 def reduce_sum(inp: torch.Tensor, n: int, nseg: int, out: torch.Tensor, scale: float = 1.0):
     L = _lib.lib()
     assert inp.dtype == torch.float32 and out.dtype == torch.float32 and inp.numel() >= n * nseg and out.numel() >= nseg
