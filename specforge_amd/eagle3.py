@@ -71,7 +71,7 @@ class _TTTStep(torch.autograd.Function):
         # buffer keeps ONE shape whether or not a batch was checked
         gp_dev = torch.cat([gp_dev.view(-1), eng._flags.to(gp_dev.device)])
         if gp_dev.is_cuda:
-            host = getattr(eng, "_upstream_host", None)      # one pinned buffer for the engine's lifetime: allocating
+            host = eng._upstream_host      # one pinned buffer for the engine's lifetime: allocating
             if host is None or host.shape != gp_dev.shape:   # pinned memory per step costs milliseconds of idle GPU
                 host = eng._upstream_host = torch.empty(gp_dev.shape, dtype=torch.float32, pin_memory=True)
             host.copy_(gp_dev, non_blocking=True)

@@ -74,6 +74,12 @@ class DraftConfig:
         )
 
 
+def rope_type(cfg) -> Optional[str]:
+    """the RoPE variant of a config -- or of its ``rope_scaling`` dict -- (HF configs name it ``rope_type``, older ones ``type``); None: plain"""
+    rs = (cfg if isinstance(cfg, dict) else getattr(cfg, "rope_scaling", None)) or {}
+    return rs.get("rope_type", rs.get("type"))
+
+
 def _yarn_correction_dim(num_rotations, dim, base, max_pos):
     return (dim * math.log(max_pos / (num_rotations * 2 * math.pi))) / (2 * math.log(base))
 
@@ -95,7 +101,7 @@ def rope_tables(cfg: DraftConfig, dtype=torch.bfloat16, n_pos: Optional[int] = N
     n_pos = cfg.max_position_embeddings + 20 if n_pos is None else int(n_pos)
     inv_freq = 1.0 / (cfg.rope_theta ** (torch.arange(0, dim, 2).float() / dim))
     rs = cfg.rope_scaling or {}
-    rtype = rs.get("rope_type", rs.get("type"))
+    rtype = rope_type(rs)
     amp = 1.0
     if rtype == "llama3":
         factor = rs.get("factor") or 1.0
@@ -332,8 +338,7 @@ class Eagle3DraftMethods:
         if S + lck > self._rope_len:
             # the reference's rotary module rebuilds its cache for seq_len = q_len + lck when that exceeds it (llama3_eagle.py:303-306,
             # 733) and keeps the rebuilt one: dynamic NTK re-derives its base from exactly that length, every other variant extends
-            rs = c.rope_scaling or {}
-            dyn = rs.get("rope_type", rs.get("type")) == "dynamic"
+            dyn = rope_type(c) == "dynamic"
             n = S + lck if dyn else max(S + lck, self._rope[0].shape[0] + 1024)
             cos, sin = rope_tables(c, torch.bfloat16, n_pos=n)
             self._rope = (cos.to(dev), sin.to(dev))

@@ -35,7 +35,7 @@ from typing import Any, Optional
 import torch
 
 from .eagle3 import Eagle3TrainStrategy, OnlineEagle3Model, loss_mask_suffix_counts, loss_mask_window_counts, usp_unpad
-from .model import DraftConfig, Eagle3DraftMethods
+from .model import DraftConfig, Eagle3DraftMethods, rope_type
 from .training import BF16Optimizer, HipDPTrainingBackend
 
 ALGORITHM_NAME = "eagle3_hip"
@@ -108,8 +108,7 @@ def check_training_topology(t, draft_config=None, mode=None) -> None:
         if c.num_attention_heads % u or c.num_key_value_heads % u:
             raise ValueError(f"training.sp_ulysses_size {u} must divide num_attention_heads ({c.num_attention_heads}) and "
                              f"num_key_value_heads ({c.num_key_value_heads})")
-        rs = c.rope_scaling or {}
-        if rs.get("rope_type", rs.get("type")) == "mrope":
+        if rope_type(c) == "mrope":
             raise ValueError("rope_scaling.rope_type 'mrope' is not supported with attention_backend 'usp' (the reference refuses it "
                              "too, llama3_eagle.py:1363-1505)")
         hd = c.head_dim or c.hidden_size // c.num_attention_heads
