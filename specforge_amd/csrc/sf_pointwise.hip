@@ -445,20 +445,26 @@ template <typename T>
 SF_GLOBAL void adamw_kernel(const T* g, float* master, float* m, float* v, T* param, long n, const float* norm,
                             float max_norm, float lr, float beta1, float beta2, float eps, float wd, float bc1,
                             float bc2_sqrt, float grad_prescale, int vec) {
+    // no contraction left to the compiler in this kernel: the two loops below inline `update` separately, and with multiply-adds contracted
+    // per loop the 8-wide and the one-per-trip launch gave different last bits on gfx950.  The three multiply-adds are fused by hand.
+#pragma clang fp contract(off)
     float clip = 1.0f;
     if (max_norm > 0.f) clip = fminf(1.0f, max_norm / (norm[0] + 1e-6f));
     const float gsc = clip * grad_prescale;
     const float step_size = lr / bc1;
+    const float decay = 1.0f - lr * wd, omb1 = 1.0f - beta1, omb2 = 1.0f - beta2;
     auto update = [&](float g32, float& p, float& mi, float& vi) {
+#pragma clang fp contract(off)
         g32 *= gsc;
-        p = p * (1.0f - lr * wd);
-        mi = mi * beta1 + g32 * (1.0f - beta1);
-        vi = vi * beta2 + g32 * g32 * (1.0f - beta2);
+        p = p * decay;
+        mi = fmaf(mi, beta1, g32 * omb1);
+        vi = fmaf(vi, beta2, g32 * g32 * omb2);
         const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        p = p - step_size * (mi / denom);
+        p = fmaf(-step_size, mi / denom, p);
     };
     // 28 bytes per parameter, nothing else: 8 parameters per thread and trip, every stream as 16-byte accesses (round 4: the scalar
-    // form -- 2- and 4-byte accesses, one parameter per trip -- ran at 4.8 TB/s; same arithmetic per element, bit-identical results)
+    // form -- 2- and 4-byte accesses, one parameter per trip -- ran at 4.8 TB/s; same arithmetic per element, bit-identical results:
+    // tests/test_optimizer_kernels.py compares the two launches)
     const long n8 = vec ? n >> 3 : 0;      // (vec = 0: some stream is not 16-byte aligned -- one parameter per trip)
     for (long u = (long)blockIdx.x * blockDim.x + threadIdx.x; u < n8; u += (long)gridDim.x * blockDim.x) {
         const long i = u * 8;

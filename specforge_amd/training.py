@@ -87,6 +87,11 @@ class BF16Optimizer:
         # ``offload_master`` (optimizer.py:25-35) moves the reference's fp32 masters and AdamW state to host memory to fit small
         # GPUs; it changes where the step runs, not what it computes.  On MI355X the 28 bytes per parameter stay in HBM (3.4 GB
         # of 288 at Llama-3-8B draft size), so the flag is accepted for config compatibility and has no effect on placement.
+        # The reference scales every gradient by clamp(max_grad_norm / (norm + 1e-6), max=1) (optimizer.py:92): 0 freezes training and
+        # a negative value turns every step around.  sf_adamw_step does not clip for max_norm <= 0.  Neither is what a config can mean.
+        if not float(max_grad_norm) > 0.0:
+            raise ValueError(f"max_grad_norm must be positive, got {max_grad_norm!r} (to train without clipping pass a bound no "
+                             "gradient norm reaches, e.g. float('inf'))")
         self.offload_master = bool(offload_master)
         if self.offload_master:
             import warnings

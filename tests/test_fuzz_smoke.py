@@ -60,3 +60,16 @@ def test_kernel_sweep_draws(emu):
     for _ in range(8):
         kind, kw = t.draw(rng, True)
         fns[kind](emu, **kw)
+
+
+def test_kernel_sweep_draws_of_the_optimizer_and_pointwise_kinds(emu):
+    """the ``adamw`` and ``pointwise`` kinds of tools/kernel_fuzz.py: the draws of those kinds among 24 seeded draws of the full sweep"""
+    t = _tool("kernel_fuzz")
+    rng = random.Random(26)
+    seen = dict(adamw=0, pointwise=0)
+    for _ in range(24):
+        kind, kw = t.draw(rng, True, True)
+        if kind in seen:
+            seen[kind] += 1
+            t.FNS[kind](emu, **kw)
+    assert seen["adamw"] >= 3 and seen["pointwise"] >= 3, seen

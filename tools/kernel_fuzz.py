@@ -1,7 +1,9 @@
 """Randomised sweep of the HBM-bound kernels against their references: fused CE (loss, in-place gradient, argmax / accuracy /
 acceptance artefacts), RMSNorm forward / backward (+ residual gradient, weight-gradient column sums), the teacher reduction on permuted
 logits and the teacher-head GEMM with its reduction epilogue -- the bodies of tests/test_kernels.py over seeded random shapes
-(row counts that are not multiples of anything, vocabularies that are multiples of 8 only, every TTT offset, hidden sizes 8 ... 8192).
+(row counts that are not multiples of anything, vocabularies that are multiples of 8 only, every TTT offset, hidden sizes 8 ... 8192);
+the clip + AdamW step with its gradient norm (tests/test_optimizer_kernels.py: any size, alignment, hyperparameter of its grid) and the
+pointwise kernels (tests/test_pointwise_kernels.py: RoPE head sizes / head counts, SwiGLU and the casts at random sizes).
 
     python tools/kernel_fuzz.py [--cases 300] [--seed 0]          (GPU box; one JSON line per failure, a summary line last)
     python tools/kernel_fuzz.py --emu --cases 20                  (this container: the SIMT interpreter, small shapes)
@@ -22,8 +24,19 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import test_kernels as TK  # noqa: E402
 
 
-def draw(rng, emu):
-    kind = rng.choice(["ce", "ce", "norm", "norm", "teacher_reduce", "teacher_gemm"])
+def draw(rng, emu, more=False):
+    """``more``: the optimizer and pointwise kinds too (off: the draws of a seed stay what they were before those kinds existed)"""
+    kind = rng.choice(["ce", "ce", "norm", "norm", "teacher_reduce", "teacher_gemm"] + (["adamw", "adamw", "pointwise"] if more else []))
+    if kind == "adamw":
+        import test_optimizer_kernels as TO
+        return kind, TO.draw_adamw(rng, n=rng.randint(1, 3000 if emu else 3_000_000))
+    if kind == "pointwise":
+        op = rng.choice(["rope", "swiglu", "movers"])
+        if op == "rope":
+            return kind, dict(op=op, dtype=rng.choice([torch.bfloat16, torch.float32]), hd=16 * rng.randint(1, 16), nheads=rng.randint(1, 8 if emu else 48))
+        if op == "swiglu":
+            return kind, dict(op=op, dtype=rng.choice([torch.bfloat16, torch.float32]), seed=rng.randrange(1 << 30), rows=rng.randint(0, 20 if emu else 5000))
+        return kind, dict(op=op, rows=rng.randint(1, 12 if emu else 700), C=8 * rng.randint(4, 20 if emu else 300))
     f32 = rng.random() < 0.35
     dtype, = (torch.float32,) if f32 else (torch.bfloat16,)
     if kind == "ce":
@@ -47,6 +60,26 @@ def draw(rng, emu):
     return kind, dict(M=M, Vt=Vt, Vd=Vd, K=K)
 
 
+def case_pointwise(dev, op, **kw):
+    import test_pointwise_kernels as TP
+    if op == "rope":
+        TP.test_rope_forward(dev, kw["dtype"], kw["hd"], kw["nheads"])
+    elif op == "swiglu":
+        gu, da, I = TP._swiglu_inputs(kw["dtype"], kw["seed"], rows_randn=kw["rows"])
+        TP._swiglu_check(dev, gu, da, I, kw["dtype"], "fuzz")
+    else:
+        TP._movers(dev, kw["rows"], kw["C"])
+
+
+def case_adamw(dev, **kw):
+    import test_optimizer_kernels as TO
+    TO.case_adamw(dev, **kw)
+
+
+FNS = dict(ce=TK.test_ce_fused, norm=TK.test_rmsnorm_fwd_bwd, teacher_reduce=TK.test_teacher_reduce_perm,
+           teacher_gemm=TK.test_gemm_nt_teacher_matches_the_stored_logits, adamw=case_adamw, pointwise=case_pointwise)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", type=int, default=300)
@@ -62,12 +95,11 @@ def main():
     else:
         _lib.lib()
         dev = "cuda"
-    fns = dict(ce=TK.test_ce_fused, norm=TK.test_rmsnorm_fwd_bwd, teacher_reduce=TK.test_teacher_reduce_perm,
-               teacher_gemm=TK.test_gemm_nt_teacher_matches_the_stored_logits)
+    fns = FNS
     t0 = time.time()
     fails, count = 0, {}
     for i in range(args.cases):
-        kind, kw = draw(rng, args.emu)
+        kind, kw = draw(rng, args.emu, True)
         count[kind] = count.get(kind, 0) + 1
         try:
             fns[kind](dev, **kw)
