@@ -73,3 +73,16 @@ def test_kernel_sweep_draws_of_the_optimizer_and_pointwise_kinds(emu):
             seen[kind] += 1
             t.FNS[kind](emu, **kw)
     assert seen["adamw"] >= 3 and seen["pointwise"] >= 3, seen
+
+
+def test_kernel_sweep_draws_of_the_float64_loss_and_norm_kinds(emu):
+    """the ``loss`` and ``norm64`` kinds of tools/kernel_fuzz.py: the draws of those kinds among 40 seeded draws of the full sweep"""
+    t = _tool("kernel_fuzz")
+    rng = random.Random(27)
+    seen = dict(loss=0, norm64=0)
+    for _ in range(40):
+        kind, kw = t.draw(rng, True, 2)
+        if kind in seen:
+            seen[kind] += 1
+            t.FNS[kind](emu, **kw)
+    assert seen["loss"] >= 4 and seen["norm64"] >= 2, seen

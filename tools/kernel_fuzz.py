@@ -2,8 +2,9 @@
 acceptance artefacts), RMSNorm forward / backward (+ residual gradient, weight-gradient column sums), the teacher reduction on permuted
 logits and the teacher-head GEMM with its reduction epilogue -- the bodies of tests/test_kernels.py over seeded random shapes
 (row counts that are not multiples of anything, vocabularies that are multiples of 8 only, every TTT offset, hidden sizes 8 ... 8192);
-the clip + AdamW step with its gradient norm (tests/test_optimizer_kernels.py: any size, alignment, hyperparameter of its grid) and the
-pointwise kernels (tests/test_pointwise_kernels.py: RoPE head sizes / head counts, SwiGLU and the casts at random sizes).
+the clip + AdamW step with its gradient norm (tests/test_optimizer_kernels.py: any size, alignment, hyperparameter of its grid), the
+pointwise kernels (tests/test_pointwise_kernels.py: RoPE head sizes / head counts, SwiGLU and the casts at random sizes) and the float64
+cases of the loss, teacher and norm kernels (tests/test_loss_kernels.py, tests/test_norm_kernels.py) at random sizes.
 
     python tools/kernel_fuzz.py [--cases 300] [--seed 0]          (GPU box; one JSON line per failure, a summary line last)
     python tools/kernel_fuzz.py --emu --cases 20                  (this container: the SIMT interpreter, small shapes)
@@ -25,8 +26,18 @@ import test_kernels as TK  # noqa: E402
 
 
 def draw(rng, emu, more=False):
-    """``more``: the optimizer and pointwise kinds too (off: the draws of a seed stay what they were before those kinds existed)"""
-    kind = rng.choice(["ce", "ce", "norm", "norm", "teacher_reduce", "teacher_gemm"] + (["adamw", "adamw", "pointwise"] if more else []))
+    """``more``: the optimizer and pointwise kinds too; ``more == 2``: the float64 loss and norm kinds as well (off: the draws of a seed stay
+    what they were before those kinds existed)"""
+    kind = rng.choice(["ce", "ce", "norm", "norm", "teacher_reduce", "teacher_gemm"] + (["adamw", "adamw", "pointwise"] if more else [])
+                      + (["loss", "loss", "norm64"] if more == 2 else []))
+    if kind == "loss":       # tests/test_loss_kernels.py; the interpreter draws V past 8200, where the unrolled loops and their remainders run
+        op = rng.choice(["ce", "lk", "teacher", "teacher_perm"])
+        V = 8 * rng.randint(2, 1100 if emu else 5200) + (rng.randint(1, 7) if op in ("lk", "teacher") and rng.random() < 0.3 else 0)
+        return kind, dict(op=op, dtype=rng.choice([torch.bfloat16, torch.float32]), V=V, seed=rng.randrange(1 << 20), pick=rng.randrange(1 << 10))
+    if kind == "norm64":     # tests/test_norm_kernels.py
+        op = rng.choice(["fwd", "bwd", "bwd2"])
+        return kind, dict(op=op, dtype=rng.choice([torch.bfloat16, torch.float32]), H=8 * rng.randint(1, 512 if op == "bwd2" else 1024),
+                          R=rng.randint(1, 40 if emu else 600), seed=rng.randrange(1 << 20), pick=rng.randrange(1 << 10))
     if kind == "adamw":
         import test_optimizer_kernels as TO
         return kind, TO.draw_adamw(rng, n=rng.randint(1, 3000 if emu else 3_000_000))
@@ -76,7 +87,45 @@ def case_adamw(dev, **kw):
     TO.case_adamw(dev, **kw)
 
 
-FNS = dict(ce=TK.test_ce_fused, norm=TK.test_rmsnorm_fwd_bwd, teacher_reduce=TK.test_teacher_reduce_perm,
+def _retry_inputs(fn, seed):
+    """the float64 cases assert two properties of their INPUT from the reference alone (no near-tie, few elements next to a rounding
+    boundary); a drawn seed that misses one is replaced by the next"""
+    from f64_helpers import InputRejected
+    for k in range(8):
+        try:
+            return fn(seed + k)
+        except InputRejected:
+            pass
+    raise AssertionError("no seed in eight gave an input the case accepts")
+
+
+def case_loss(dev, op, dtype, V, seed, pick):
+    import test_loss_kernels as TL
+    if op == "ce":
+        form = ["p", "zt", "zt_rows"][pick % 3]
+        _retry_inputs(lambda s: TL.case_ce(dev, dtype, V, form, [0, 2][pick % 2] if form == "zt" else [0, 2, TL.T][pick % 3], seed=s), seed)
+    elif op == "lk":
+        compact, St = TL.LK_VARIANTS[pick % 4]
+        _retry_inputs(lambda s: TL.case_lk(dev, dtype, max(V, 136), "zt", compact=compact, St=St, off=1 + pick % 2, seed=s), seed)
+    elif op == "teacher":
+        V = max(V, 64)
+        TL.case_teacher(dev, dtype, V, max(3, min(V // 3, 2000 + pick % 100)), seed=seed)
+    else:
+        V = max(V, 64)
+        nparts = pick % 3
+        TL.case_teacher_perm(dev, dtype, V + 128 * nparts, 8 * max(1, min(V // 24, 250 + pick % 10)), nparts, tp=pick % 2 == 0, seed=seed)
+
+
+def case_norm64(dev, op, dtype, H, R, seed, pick):
+    import test_norm_kernels as TN
+    if op == "fwd":
+        _retry_inputs(lambda s: TN.case_fwd(dev, dtype, R, H, seed=s), seed)
+    else:
+        _retry_inputs(lambda s: TN.case_bwd(dev, dtype, R, H, two=op == "bwd2", add=pick % 2 == 0, dw_mode=pick % 3,
+                                            want_dx=op == "bwd2" or pick % 5 != 4, seed=s), seed)
+
+
+FNS = dict(loss=case_loss, norm64=case_norm64, ce=TK.test_ce_fused, norm=TK.test_rmsnorm_fwd_bwd, teacher_reduce=TK.test_teacher_reduce_perm,
            teacher_gemm=TK.test_gemm_nt_teacher_matches_the_stored_logits, adamw=case_adamw, pointwise=case_pointwise)
 
 
@@ -99,7 +148,7 @@ def main():
     t0 = time.time()
     fails, count = 0, {}
     for i in range(args.cases):
-        kind, kw = draw(rng, args.emu, True)
+        kind, kw = draw(rng, args.emu, 2)
         count[kind] = count.get(kind, 0) + 1
         try:
             fns[kind](dev, **kw)
