@@ -227,6 +227,19 @@ int sf_colsum_accum(const float* partial, int nb, int H, float* acc, int accumul
 int sf_rope(void* x, int dtype, long ld, int rows, int nheads, int hd, const void* cos_t, const void* sin_t,
             const long long* pos_ids, int pos_off, int max_pos, int backward, void* stream);
 
+/* Multimodal RoPE with the angles computed on the device (LlamaMutiRotaryEmbedding.forward, llama3_eagle.py:389-427, with
+ * apply_multimodal_rotary_pos_emb 145-182): no cos / sin table and no upper limit on the ids.  Channel pair d of a head (columns d and
+ * d + hd/2) reads position axis axis[d] (0 / 1 / 2) of pos3 [3, rows]:
+ *   angle = (float)(pos3[axis[d]][row] + pos_off) * inv_freq[d]      one fp32 product, the int64 -> fp32 conversion rounds to nearest
+ *   cos / sin = round_T(cosf / sinf(angle) * scale)                  accurate single-precision functions, full range reduction
+ * then the rotation of sf_rope (forward / transposed): with equal cos / sin bits the output bits are sf_rope's.  inv_freq [hd/2] fp32 and
+ * scale are the values a cos / sin table would be built from.  The hd/2 angles of a row are computed once, not once per head.
+ * A row with a negative id on any axis (after pos_off) is not rotated by a wrapped or clamped angle: its nheads * hd columns are zeroed
+ * and 1.0f is written to *flag (optional, may be NULL).  Same shape rules as sf_rope (hd % 16 == 0, ld % 8 == 0; hd <= 1024); rows == 0
+ * is a no-op.  Additive in ABI 6. */
+int sf_rope_mrope(void* x, int dtype, long ld, int rows, int nheads, int hd, const float* inv_freq, const int* axis,
+                  const long long* pos3, int pos_off, float scale, int backward, float* flag, void* stream);
+
 /* ---- Ulysses sequence parallelism (attention_backend "usp", batch 1; llama3_eagle.py:1363-1505), ABI 6 additions.
  * Send / receive layout [sp][chunk][w]: block j holds rank j's heads (q | k | v groups of nh/sp, nkv/sp heads) of this rank's tokens;
  * received, it is the head-sharded [sp*chunk, w] operand of the attention kernels.

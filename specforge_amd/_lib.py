@@ -53,6 +53,7 @@ _SIGS = {
     "sf_colsum_accum": (c_int, [P, c_int, c_int, P, c_int, P]),
     "sf_rows_expand": (c_int, [P, c_int, c_long, P, P, c_long, c_long, c_int, P]),
     "sf_rope": (c_int, [P, c_int, c_long, c_int, c_int, c_int, P, P, P, c_int, c_int, c_int, P]),
+    "sf_rope_mrope": (c_int, [P, c_int, c_long, c_int, c_int, c_int, P, P, P, c_int, c_float, c_int, P, P]),
     "sf_ulysses_pack_qkv": (c_int, [P, c_long, P, c_long, c_int, c_int, c_int, c_int, c_int, P, P, P, c_int, c_int, c_int, P]),
     "sf_ulysses_pack_o": (c_int, [P, c_long, P, c_long, c_int, c_int, c_int, P]),
     "sf_ulysses_unpack_o": (c_int, [P, c_long, P, c_long, c_int, c_int, c_int, P]),

@@ -327,6 +327,76 @@ SF_GLOBAL void rope_kernel(T* x, long ld, int nheads, int hd, const T* cos_t, co
     }
 }
 
+// Analytic multimodal RoPE (LlamaMutiRotaryEmbedding.forward, llama3_eagle.py:389-427: inv_freq * position_id in fp32, cos / sin, cast):
+// channel pair d of a head (columns d and d + hd/2) takes its angle from position axis axis[d] of pos3 [3, rows] -- no table, no limit
+// on the ids.  The hd/2 angles of a token row are computed once per row (one workgroup per row, as rope_kernel) and laid down in LDS as the
+// row of a per-token table rope_kernel would read (scaled, rounded to T, both halves); then every head rotates with them exactly as
+// rope_kernel does -- the same loads and expressions: with equal cos / sin bits, rope_kernel's bits.
+// A row with a negative id on any axis (after pos_off) is zeroed and *flag set: never rotated by a wrapped or clamped angle.
+constexpr int kMropeMaxHalf = 512;      // hd <= 1024 (the engine's attention stops at 256)
+
+// one fp32 product that no later operation may absorb (the library is built with -ffp-contract=fast)
+SF_DEVICE float sf_mul_unfused(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+
+template <typename T>
+SF_GLOBAL void rope_mrope_kernel(T* x, long ld, int rows, int nheads, int hd, const float* inv_freq, const int* axis,
+                                 const long long* pos3, int pos_off, float scale, int backward, float* flag) {
+    SF_SHARED __attribute__((aligned(16))) T cs[2 * kMropeMaxHalf];     // this row of a per-token cos / sin table, both halves
+    SF_SHARED __attribute__((aligned(16))) T sn[2 * kMropeMaxHalf];
+    const int r = (int)blockIdx.x;
+    const int half = hd >> 1, upr = half >> 3;  // 8-wide units per head-half
+    T* xr = x + (long)r * ld;
+    const long long p0 = pos3[r] + pos_off, p1_ = pos3[(long)rows + r] + pos_off, p2_ = pos3[2 * (long)rows + r] + pos_off;
+    if (p0 < 0 || p1_ < 0 || p2_ < 0) {      // (uniform over the workgroup)
+        if (threadIdx.x == 0 && flag) *flag = 1.0f;
+        const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        for (int u = (int)threadIdx.x; u < nheads * (hd >> 3); u += (int)blockDim.x) SfVec8<T>::st(xr + u * 8, z);
+        return;
+    }
+    for (int d = (int)threadIdx.x; d < half; d += (int)blockDim.x) {
+        const int a = axis[d];
+        const long long p = a == 0 ? p0 : (a == 1 ? p1_ : p2_);
+        const float ang = sf_mul_unfused((float)p, inv_freq[d]);    // int64 -> fp32 rounds to nearest even, as .float() does
+        float s, c;
+        sincosf(ang, &s, &c);                   // full range reduction: angles reach 1e6 and beyond
+        c = sf_mul_unfused(c, scale);
+        s = sf_mul_unfused(s, scale);
+        SfElem<T>::st(cs + d, c);
+        SfElem<T>::st(cs + half + d, c);
+        SfElem<T>::st(sn + d, s);
+        SfElem<T>::st(sn + half + d, s);
+    }
+    sf_syncthreads();
+    for (int u = (int)threadIdx.x; u < nheads * upr; u += (int)blockDim.x) {
+        const int h = u / upr, j = (u - h * upr) * 8;
+        T* p1 = xr + h * hd + j;
+        T* p2 = p1 + half;
+        float x1[8], x2[8], c1[8], c2[8], s1[8], s2[8], o1[8], o2[8];
+        SfVec8<T>::ld(p1, x1);
+        SfVec8<T>::ld(p2, x2);
+        SfVec8<T>::ld(cs + j, c1);
+        SfVec8<T>::ld(cs + half + j, c2);
+        SfVec8<T>::ld(sn + j, s1);
+        SfVec8<T>::ld(sn + half + j, s2);
+        // rope_kernel's loads and expressions, in its order (tests/test_mrope_analytic.py holds the two kernels to equal bits)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            if (!backward) {
+                o1[i] = SfElem<T>::rnd(x1[i] * c1[i]) + SfElem<T>::rnd(-x2[i] * s1[i]);
+                o2[i] = SfElem<T>::rnd(x2[i] * c2[i]) + SfElem<T>::rnd(x1[i] * s2[i]);
+            } else {
+                o1[i] = x1[i] * c1[i] + x2[i] * s2[i];
+                o2[i] = x2[i] * c2[i] - x1[i] * s1[i];
+            }
+        }
+        SfVec8<T>::st(p1, o1);
+        SfVec8<T>::st(p2, o2);
+    }
+}
+
 // ------------------------------------------------------------------- SwiGLU
 template <typename T>
 SF_GLOBAL void swiglu_fwd_kernel(const T* gu, long ldgu, int I, long rows, T* act, long ldact) {
@@ -605,6 +675,15 @@ extern "C" int sf_rope(void* x, int dtype, long ld, int rows, int nheads, int hd
     SF_DISPATCH_T(dtype, SF_LAUNCH((rope_kernel<T>), dim3(rows), dim3(256), 0, stream, (T*)x, ld, nheads, hd, (const T*)cos_t,
                                    (const T*)sin_t, pos_ids, pos_off, max_pos, backward));
     return sf_check_launch("sf_rope");
+}
+
+extern "C" int sf_rope_mrope(void* x, int dtype, long ld, int rows, int nheads, int hd, const float* inv_freq, const int* axis,
+                             const long long* pos3, int pos_off, float scale, int backward, float* flag, void* stream) {
+    SF_CHECK_ARG(rows >= 0 && nheads > 0 && hd > 0 && hd % 16 == 0 && hd <= 2 * kMropeMaxHalf && ld % 8 == 0, "sf_rope_mrope: bad shape");
+    if (rows == 0) return 0;
+    SF_DISPATCH_T(dtype, SF_LAUNCH((rope_mrope_kernel<T>), dim3(rows), dim3(256), 0, stream, (T*)x, ld, rows, nheads, hd, inv_freq, axis,
+                                   pos3, pos_off, scale, backward, flag));
+    return sf_check_launch("sf_rope_mrope");
 }
 
 extern "C" int sf_swiglu_fwd(const void* gu, int dtype, long ldgu, long rows, int I, void* act, long ldact, void* stream) {

@@ -105,11 +105,12 @@ class OnlineEagle3Model(nn.Module):
 
     def __init__(self, draft_model: LlamaForCausalLMEagle3, length: int = 7, attention_backend: str = "hip",
                  lk_loss_type: Optional[str] = None, kl_scale: float = 1.0, kl_decay: float = 1.0,
-                 ploss_decay: float = 0.8, sp_group=None, sp_ulysses_group=None, sp_ring_group=None):
+                 ploss_decay: float = 0.8, sp_group=None, sp_ulysses_group=None, sp_ring_group=None, mrope_analytic: bool = False):
         """``attention_backend="usp"``: Ulysses sequence parallelism over ``sp_group`` (set here, or later by
         ``HipDPTrainingBackend.prepare_model`` / the strategy, before the first forward); every other value runs the one-rank
         attention.  ``sp_ring_group`` (with ``sp_ulysses_group``, None for a pure ring): ring x Ulysses over the same SP group
-        (training.make_usp_groups); ``sp_group`` alone is pure Ulysses."""
+        (training.make_usp_groups); ``sp_group`` alone is pure Ulysses.  ``mrope_analytic``: ``Eagle3Engine.mrope_analytic`` (rope_type
+        'mrope': angles computed on the device from the ids -- no table limits; off by default)."""
         super().__init__()
         if lk_loss_type not in (None, "alpha", "lambda"):
             raise ValueError(f"Unknown lk loss type: {lk_loss_type}")  # core/lk_loss.py:99
@@ -122,6 +123,7 @@ class OnlineEagle3Model(nn.Module):
         self.sp_ulysses_group, self.sp_ring_group = sp_ulysses_group, sp_ring_group
         self.lk_loss_type, self.kl_scale, self.kl_decay = lk_loss_type, kl_scale, kl_decay
         self.ploss_decay = ploss_decay
+        self.mrope_analytic = mrope_analytic
         self._engine: Optional[Eagle3Engine] = None
         dev = next(draft_model.parameters()).device
         self._anchor = nn.Parameter(torch.zeros((), device=dev), requires_grad=True)
@@ -140,7 +142,8 @@ class OnlineEagle3Model(nn.Module):
                 sp_group, uly_group, ring_group = self.sp_group, self.sp_ulysses_group, self.sp_ring_group
             self._engine = Eagle3Engine(self.draft_model, ttt_length=self.length, ploss_decay=self.ploss_decay,
                                         lk_loss_type=self.lk_loss_type, kl_scale=self.kl_scale, kl_decay=self.kl_decay,
-                                        sp_group=sp_group, sp_ulysses_group=uly_group, sp_ring_group=ring_group)
+                                        sp_group=sp_group, sp_ulysses_group=uly_group, sp_ring_group=ring_group,
+                                        mrope_analytic=self.mrope_analytic)
             object.__setattr__(self.draft_model, "_hip_engine", self._engine)   # found by BF16Optimizer(draft_model)
         return self._engine
 

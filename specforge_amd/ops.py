@@ -324,6 +324,21 @@ def rope_(x: torch.Tensor, nheads: int, hd: int, cos_t: torch.Tensor, sin_t: tor
     return x
 
 
+def rope_mrope(x: torch.Tensor, nheads: int, hd: int, inv_freq: torch.Tensor, axis: torch.Tensor, pos3: torch.Tensor, pos_off: int,
+               scale: float = 1.0, backward: bool = False, flag: Optional[torch.Tensor] = None):
+    """in place on the first nheads*hd columns of the 2-D view x: multimodal RoPE with the angles computed on the device from the
+    three-axis ids ``pos3`` [3, rows] int64 (sf_rope_mrope) -- ``inv_freq`` [hd/2] fp32, ``axis`` [hd/2] int32 (which axis channel
+    pair d reads).  ``flag`` (one fp32 element): set to 1 when a row has a negative id (that row is zeroed, not rotated)."""
+    L = _lib.lib()
+    assert inv_freq.dtype == torch.float32 and axis.dtype == torch.int32 and pos3.dtype == torch.int64
+    assert inv_freq.is_contiguous() and axis.is_contiguous() and pos3.is_contiguous()
+    assert inv_freq.numel() == hd // 2 and axis.numel() == hd // 2 and tuple(pos3.shape) == (3, x.shape[0]) and x.shape[1] >= nheads * hd
+    assert flag is None or (flag.dtype == torch.float32 and flag.numel() == 1)
+    _lib.check(L.sf_rope_mrope(_p(x), _dt(x), _rowmajor(x), x.shape[0], nheads, hd, _p(inv_freq), _p(axis), _p(pos3), pos_off,
+                               float(scale), 1 if backward else 0, _p(flag), _stream()), "sf_rope_mrope")
+    return x
+
+
 def ulysses_pack_qkv(src: torch.Tensor, dst: torch.Tensor, *, sp: int, nh: int, nkv: int, hd: int, cos_t: torch.Tensor,
                      sin_t: torch.Tensor, pos_ids: torch.Tensor, pos_off: int, backward: bool = False):
     """Ulysses exchange image of one TTT step's q | k | v (batch 1).  forward: token rows src [chunk, (nh+2nkv)*hd] -> dst
