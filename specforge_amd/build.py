@@ -28,8 +28,6 @@ def _deps():
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     hdrs.append(os.path.join(ROOT, "include", "specforge_amd.h"))
     hdrs.append(os.path.join(ROOT, "tests", "emu", "sf_emu.h"))
-    exp = os.path.join(ROOT, "tools", "experiments")
-    hdrs += [os.path.join(exp, f) for f in os.listdir(exp) if f.endswith(".inc")]
     return [h for h in hdrs if os.path.exists(h)]
 
 
@@ -76,25 +74,15 @@ def _build(lib, objdir, compile_cmd, link_cmd, force=False):
     return lib
 
 
+# hipcc flags of the product library (tools/isa_diff.py compiles with the same)
+HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-x", "hip", "-I", CSRC,
+             "-Wno-unused-result", "-ffp-contract=fast"]
+
+
 def build_hip(force=False, verbose=False):
     """hipcc --offload-arch=gfx950 -> specforge_amd/libsfhip.so"""
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-x", "hip", "-I", CSRC,
-             "-Wno-unused-result", "-ffp-contract=fast"]
-    lib = _build(HIP_LIB, os.path.join(ROOT, "build", "hip"), [HIPCC] + flags,
+    lib = _build(HIP_LIB, os.path.join(ROOT, "build", "hip"), [HIPCC] + HIP_FLAGS,
                  [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC"], force)
-    if verbose:
-        print("built", lib)
-    return lib
-
-
-def build_ablate(force=False, verbose=False):
-    """TOOLS ONLY: hipcc -DSF_ABLATE -> tools/experiments/libsfhip_ablate.so -- the measured-and-rejected kernel variants
-    and the SF_* environment knobs that select them (A/B timing; some give wrong results by design).  Never loaded by the
-    package; tools inject it with ``_lib._inject_library_for_tests``."""
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-x", "hip", "-I", CSRC, "-DSF_ABLATE",
-             "-Wno-unused-result", "-ffp-contract=fast"]
-    lib = _build(os.path.join(ROOT, "tools", "experiments", "libsfhip_ablate.so"), os.path.join(ROOT, "build", "ablate"),
-                 [HIPCC] + flags, [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC"], force)
     if verbose:
         print("built", lib)
     return lib
@@ -123,7 +111,5 @@ if __name__ == "__main__":
         build_hip(force="--force" in what, verbose=True)
     if "emu" in what:
         build_emu(force="--force" in what, verbose=True)
-    if "ablate" in what:
-        build_ablate(force="--force" in what, verbose=True)
     if "asan" in what:
         build_emu(force="--force" in what, asan=True, verbose=True)

@@ -23,12 +23,6 @@ using namespace sfattn;
 
 namespace {
 
-#ifdef SF_ABLATE   // profiling experiments of the tools build: 1 = stage tile 0 only, 2 = skip the MFMA / softmax work
-#define SF_ATTN_DBG(p, bit) ((p).dbg & (bit))
-#else
-#define SF_ATTN_DBG(p, bit) false
-#endif
-
 // ------------------------------------------------------------------ forward
 // -inf where the tile-relative key index `c` is past `rel` (= last visible key - first key of the block - 4 * hi)
 SF_DEVICE void mask_scores(sf_v16f& s, int rel) {
@@ -38,7 +32,8 @@ SF_DEVICE void mask_scores(sf_v16f& s, int rel) {
 }
 
 template <int HD, int NW>
-SF_GLOBAL void SF_LAUNCH_BOUNDS(NW * 64, AttnOcc<HD>::kWgPerCu) attn_fwd_kernel(AttnFwdArgs p) {
+SF_GLOBAL void SF_LAUNCH_BOUNDS(NW * 64, 2) attn_fwd_kernel(AttnFwdArgs p) {
+    static_assert(HD <= 128, "head_dim 256 has its own kernel (sf_attn_w1.hip)");
     constexpr int KS = HD / 16, DB = HD / 32, QB = NW * 32, TILE = 128 * HD * 2;
     SF_DYN_SMEM(smem);  // 2 x { K [64][HD], V [64][HD] }
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = sf_wave_id(), c = lane & 31, hi = lane >> 5;
@@ -100,7 +95,7 @@ SF_GLOBAL void SF_LAUNCH_BOUNDS(NW * 64, AttnOcc<HD>::kWgPerCu) attn_fwd_kernel(
         const int key0 = kt * 64;
         sf_wait_vm0();
         sf_syncthreads();  // tile kt landed for everyone; buffer (kt+1)&1 is no longer being read
-        if (kt + 1 < ntiles && !SF_ATTN_DBG(p, 1)) {
+        if (kt + 1 < ntiles) {
             char* nb = smem + ((kt + 1) & 1) * TILE;
             st.issue(kbuf, (unsigned)(kt + 1) * tile_bytes, nb);
             st.issue(vbuf, (unsigned)(kt + 1) * tile_bytes, nb + 64 * HD * 2);
@@ -108,7 +103,6 @@ SF_GLOBAL void SF_LAUNCH_BOUNDS(NW * 64, AttnOcc<HD>::kWgPerCu) attn_fwd_kernel(
         const char* lds_k = smem + (kt & 1) * TILE;
         const char* lds_v = lds_k + 64 * HD * 2;
         if (key0 > qg0 + 31) continue;  // whole tile above this wave's diagonal (wave-uniform)
-        if (SF_ATTN_DBG(p, 2)) continue;
         const bool need_mask = (key0 + 63 > qg0) || (key0 + 63 >= kvlen);
         sf_v16f s[2];
 #pragma unroll
@@ -186,7 +180,6 @@ SF_GLOBAL void SF_LAUNCH_BOUNDS(NW * 64, AttnOcc<HD>::kWgPerCu) attn_fwd_kernel(
         for (int i = 0; i < p.ndiag; ++i) {
             sf_wait_vm0();
             sf_wave_lockstep();   // (interpreter only: the other lanes' pieces of this wave's DMA have been copied)
-            if constexpr (HD <= 128) {
             sf_v8s kk[KS];
             sf_v4s vv4[DB * 4];
 #pragma unroll
@@ -228,33 +221,6 @@ SF_GLOBAL void SF_LAUNCH_BOUNDS(NW * 64, AttnOcc<HD>::kWgPerCu) attn_fwd_kernel(
                     }
                 }
                 acc_o[d] = acc_o[d] * alpha + vf * e;
-            }
-            } else {
-            // head_dim 256: the query fragments and the output accumulators are 192 registers of the wave already -- the branch's
-            // K_i / V_i rows are consumed from LDS a few registers at a time, and the next branch is staged only after the last read
-            float dp = 0.f;
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) dp += dot8(qf[ks], frag_rows<HD>(mine, 0, ks, fo));
-            dp = sf_pair_sum(dp);
-            const float s2 = dp * sc;
-            const float mn = fmaxf(m, s2);
-            const float alpha = sf_exp2(m - mn);
-            const float e = sf_exp2(s2 - mn);
-            m = mn;
-            l = l * alpha + e;
-            const char* vrow = mine + 32 * HD * 2 + c * (HD * 2) + 8 * hi;
-#pragma unroll
-            for (int d = 0; d < DB; ++d)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const sf_v4s vv = *reinterpret_cast<const sf_v4s*>(vrow + (((4 * d + j) ^ swz<HD>(c)) << 4));
-#pragma unroll
-                    for (int t = 0; t < 4; ++t)
-                        acc_o[d][4 * j + t] = acc_o[d][4 * j + t] * alpha + e * sf_bf2f((sf_bf16)vv[t]);
-                }
-#pragma unroll
-            for (int d = 0; d < DB; ++d) sf_pin(acc_o[d]);       // every LDS read of this branch has returned
-            if (i + 1 < p.ndiag) stage_diag(i + 1);
             }
         }
     }
@@ -614,7 +580,8 @@ SF_GLOBAL void SF_LAUNCH_BOUNDS(256, 2) attn_bwd_diag_kernel(AttnBwdDiagArgs p) 
 // ------------------------------------------------------------- backward: dQ
 
 template <int HD, int NW>
-SF_GLOBAL void SF_LAUNCH_BOUNDS(NW * 64, AttnOcc<HD>::kWgPerCu) attn_bwd_dq_kernel(AttnBwdArgs p) {
+SF_GLOBAL void SF_LAUNCH_BOUNDS(NW * 64, 2) attn_bwd_dq_kernel(AttnBwdArgs p) {
+    static_assert(HD <= 128, "head_dim 256 has its own kernel (sf_attn_w1.hip)");
     constexpr int KS = HD / 16, DB = HD / 32, QB = NW * 32, TILE = 128 * HD * 2;
     SF_DYN_SMEM(smem);  // 2 x { K [64][HD], V [64][HD] }; K serves both S^T = K.Q^T and (transpose-read) dQ^T += K^T.dS^T
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = sf_wave_id(), c = lane & 31, hi = lane >> 5;
@@ -747,10 +714,6 @@ SF_GLOBAL void SF_LAUNCH_BOUNDS(NW * 64, AttnOcc<HD>::kWgPerCu) attn_bwd_dq_kern
 
 }  // namespace
 
-#if defined(SF_ABLATE) && !defined(SF_EMU)
-#include "../../tools/experiments/sf_attn_w4_variants.inc"
-#endif
-
 constexpr int kAttnFwdWaves = 4;
 
 // S = local queries; the key buffers hold q_off + S rows per batch (sf_attn_common.h: query offset)
@@ -769,19 +732,14 @@ static int attn_fwd_entry(const void* q, long ldq, const void* k0, long ldk, con
     p.ndiag = ndiag; p.kv_len = kv_len;
     p.o = (sf_bf16*)o; p.ldo = ldo; p.lse = lse;
     p.B = B; p.S = S; p.nh = nh; p.nkv = nkv; p.scale = scale; p.q_off = q_off;
-    p.dbg = sf_knob("SF_ATTN_DBG", 0);
-    p.l2_map = sf_knob("SF_ATTN_L2MAP", 1);
+    p.l2_map = 1;   // (a product constant kept as a kernel argument: DESIGN section 7)
     SF_CHECK_ARG(((long)q_off + S) * ldk * 2 < (1L << 31), "sf_attn_fwd: S * ldk exceeds the 2 GiB range of a buffer descriptor");
     constexpr int NW = kAttnFwdWaves;
     const long nqb = (S + NW * 32 - 1) / (NW * 32);
-    dim3 grid(p.l2_map ? attn_pair_major_grid(nqb * (nh / nkv), (long)nkv * B) : (unsigned)(nqb * nh * B));
-#if defined(SF_ABLATE) && !defined(SF_EMU)
-    if (q_off == 0 && sf_knob("SF_ATTN_FWD_W4", 0))   // tools build: the measured-and-rejected one-wave-per-SIMD variant
-        return sfattn_w4::attn_fwd(q, ldq, k0, ldk, v0, kd, vd, ndiag, kv_len, o, ldo, lse, B, S, nh, nkv, hd, scale, stream);
-#endif
-    // head_dim 256: one wave per SIMD, slot-planned (sf_attn_w1.hip); the generic instantiation stays as the tools build's A/B
-    if (hd == 256 && sf_knob("SF_ATTN_W1", 1)) return attn_fwd_w1_launch(p, hd, stream);
-    SF_HD_DISPATCH(hd, SF_ALLOW_SMEM((attn_fwd_kernel<HD, NW>), 2 * 128 * HD * 2);
+    dim3 grid(attn_pair_major_grid(nqb * (nh / nkv), (long)nkv * B));
+    // head_dim 256: one wave per SIMD, slot-planned (sf_attn_w1.hip)
+    if (hd == 256) return attn_fwd_w1_launch(p, hd, stream);
+    SF_HD_DISPATCH_64_128(hd, SF_ALLOW_SMEM((attn_fwd_kernel<HD, NW>), 2 * 128 * HD * 2);
                    SF_LAUNCH((attn_fwd_kernel<HD, NW>), grid, dim3(NW * 64), 2 * 128 * HD * 2, stream, p));
     return sf_check_launch("sf_attn_fwd");
 }
@@ -895,7 +853,7 @@ static int fill_bwd_args(AttnBwdArgs& p, const void* q, long ldq, const void* do
     p.dq = (sf_bf16*)dq; p.lddq = lddq;
     p.dk = dk; p.dv = dv; p.lddk = lddk;
     p.B = B; p.S = S; p.nh = nh; p.nkv = nkv; p.scale = scale; p.q_off = q_off;
-    p.l2_map = sf_knob("SF_ATTN_L2MAP", 1);
+    p.l2_map = 1;   // (a product constant kept as a kernel argument: DESIGN section 7)
     return 0;
 }
 
@@ -906,11 +864,6 @@ static int attn_bwd_dq_entry(const void* q, long ldq, const void* dout, long ldd
     SF_CHECK_ARG(B > 0 && S > 0 && nh > 0 && nkv > 0 && nh % nkv == 0, "sf_attn_bwd_dq: bad shape");
     SF_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && lddo % 8 == 0 && lddq % 8 == 0,
                  "sf_attn_bwd_dq: row strides must be multiples of 8 (16-byte segments)");
-#if defined(SF_ABLATE) && !defined(SF_EMU)
-    if (q_off == 0 && sf_knob("SF_ATTN_DQ_W4", 0))    // tools build: the measured-and-rejected one-wave-per-SIMD variant
-        return sfattn_w4::attn_bwd_dq(q, ldq, dout, lddo, k0, ldk, v0, ldv, kv_len, lse, delta, dq_init, dq, lddq, B, S, nh, nkv, hd,
-                                      scale, stream);
-#endif
     AttnBwdArgs p;
     fill_bwd_args(p, q, ldq, dout, lddo, k0, ldk, v0, ldv, kv_len, lse, delta, dq_init, dq, lddq,
                   nullptr, nullptr, 0, B, S, nh, nkv, scale, q_off);
@@ -918,9 +871,9 @@ static int attn_bwd_dq_entry(const void* q, long ldq, const void* dout, long ldd
                  "sf_attn_bwd_dq: S * ld exceeds the 2 GiB range of a buffer descriptor");
     constexpr int NW = kAttnFwdWaves;
     const long nqb = (S + NW * 32 - 1) / (NW * 32);
-    dim3 grid(p.l2_map ? attn_pair_major_grid(nqb * (nh / nkv), (long)nkv * B) : (unsigned)(nqb * nh * B));
-    if (hd == 256 && sf_knob("SF_ATTN_W1", 1)) return attn_bwd_dq_w1_launch(p, hd, stream);    // (sf_attn_w1.hip)
-    SF_HD_DISPATCH(hd, SF_ALLOW_SMEM((attn_bwd_dq_kernel<HD, NW>), 2 * 128 * HD * 2);
+    dim3 grid(attn_pair_major_grid(nqb * (nh / nkv), (long)nkv * B));
+    if (hd == 256) return attn_bwd_dq_w1_launch(p, hd, stream);    // (sf_attn_w1.hip)
+    SF_HD_DISPATCH_64_128(hd, SF_ALLOW_SMEM((attn_bwd_dq_kernel<HD, NW>), 2 * 128 * HD * 2);
                    SF_LAUNCH((attn_bwd_dq_kernel<HD, NW>), grid, dim3(NW * 64), 2 * 128 * HD * 2, stream, p));
     return sf_check_launch("sf_attn_bwd_dq");
 }

@@ -66,8 +66,8 @@ struct AttnFwdArgs {
     float* lse;                        // [B, nh, S] natural-log lse over all S+k columns
     int B, S, nh, nkv;
     float scale;
-    int l2_map;  // pair-major work order (attn_work_index); 0 only in the tools build's A/B
-    int dbg;  // profiling experiments only (SF_ATTN_DBG): 1 = stage tile 0 only, 2 = skip the MFMA/softmax work
+    int l2_map;  // pair-major work order (attn_pair_major_index); always 1
+    int dbg;     // unused (always 0): kept so that the fields behind it stay where the compiled kernels read them
     int q_off;   // ring shard: the S local queries sit at global positions q_off.. and k0 / v0 hold q_off + S rows per batch (see below)
 };
 
@@ -107,10 +107,6 @@ template <int HD>
 SF_DEVICE int swz(int r) {
     return HD >= 128 ? (((r & 3) << 2) ^ ((r >> 2) & 3)) : (r & 7);
 }
-// Workgroups per CU of the MFMA attention kernels (fwd, dQ): two 4-wave workgroups (2 waves per SIMD, 256 registers each) up to
-// head_dim 128; at head_dim 256 the output accumulators alone are 128 registers per wave and the K / V ring is 128 KiB of LDS:
-// one workgroup per CU with the whole register file.
-template <int HD> struct AttnOcc { static constexpr int kWgPerCu = HD > 128 ? 1 : 2; };
 
 // ---- LDS tile staging -------------------------------------------------------
 // A tile of R rows x HD (row-major in LDS, 16-byte chunks XOR-swizzled by swz<HD>(row)) arrives as R*HD*2/1024 pieces
@@ -146,9 +142,6 @@ struct TileStage {
         }
     }
 };
-// dK/dV kernel: wait until at most ONE tile's worth of this wave's DMA pieces (Q + dO pieces + 1 bookkeeping piece) is outstanding
-template <int HD>
-SF_DEVICE void sf_wait_vm_tile() { sf_wait_vmcnt<2 * TileStage<HD, 64, 4>::NI + 1>(); }
 // descriptor over the rows [0, S) of one (batch, head) slice: base = first row, row stride ld elements
 template <int HD>
 SF_DEVICE SfBufB rows_buf(const sf_bf16* base, long ld, int S) {
@@ -356,35 +349,6 @@ struct AgprBank {
 };
 
 
-// ---- TOOLS BUILD ONLY: cycle stamps inside the slot-planned tile loops ---------------------------------------------
-// SfProf<PROF> accumulates s_memtime deltas between marks into 16 per-wave sums and flushes them to a device buffer
-// (sf_tool_attn_prof); PROF = 0 (always, in the product library) compiles to nothing.  The streams are pinned by
-// SF_SCHED_FENCE already, so the stamps (one SMEM instruction + two scalar adds each) barely move them.
-#if defined(SF_ABLATE) && !defined(SF_EMU)
-extern __device__ unsigned long long* g_attn_prof;
-template <int PROF> struct SfProf {
-    unsigned t[12], last, rt0;   // 32-bit sums: the whole lifetime of a workgroup is < 2^32 ticks (and SGPRs are scarce)
-    SF_DEVICE void start() {
-        if (PROF) { for (int i = 0; i < 12; ++i) t[i] = 0; __builtin_amdgcn_sched_barrier(0); rt0 = (unsigned)__builtin_amdgcn_s_memrealtime(); last = (unsigned)__builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
-    }
-    template <int I> SF_DEVICE void mark() {
-        if (PROF) { __builtin_amdgcn_sched_barrier(0); const unsigned x = (unsigned)__builtin_amdgcn_s_memtime(); t[I] += x - last; last = x; __builtin_amdgcn_sched_barrier(0); }
-    }
-    SF_DEVICE void flush(long slot, int lane) {
-        if (PROF) {
-            const unsigned span = (unsigned)__builtin_amdgcn_s_memrealtime() - rt0;
-            if (g_attn_prof && lane == 0) { for (int i = 0; i < 12; ++i) g_attn_prof[slot * 16 + i] = t[i]; g_attn_prof[slot * 16 + 15] = span; }
-        }
-    }
-};
-#else
-template <int PROF> struct SfProf {
-    SF_DEVICE void start() {}
-    template <int I> SF_DEVICE void mark() {}
-    SF_DEVICE void flush(long, int) {}
-};
-#endif
-
 }  // namespace sfattn
 
 #ifdef SF_EMU
@@ -418,10 +382,10 @@ int attn_bwd_dkv_w1_launch(const AttnBwdArgs& p, int hd, void* stream);
         else SF_CHECK_ARG(false, "head_dim must be 64, 128 or 256"); \
     } while (0)
 
-// (tools-build variants that exist for head_dim 64 / 128 only)
-#define SF_HD_DISPATCH_128(hd, CALL)                              \
+// (the generic forward and dQ kernels: head_dim 256 went to its own launchers before this)
+#define SF_HD_DISPATCH_64_128(hd, CALL)                           \
     do {                                                          \
         if ((hd) == 128) { constexpr int HD = 128; CALL; }        \
         else if ((hd) == 64) { constexpr int HD = 64; CALL; }     \
-        else SF_CHECK_ARG(false, "this variant exists for head_dim 64 and 128 only"); \
+        else SF_CHECK_ARG(false, "head_dim must be 64, 128 or 256"); \
     } while (0)

@@ -129,18 +129,6 @@ SF_GLOBAL void SF_LAUNCH_BOUNDS(256, 2) gemm_nt_kernel(GemmArgs p) {
 int sf_gemm_nt_256_launch(const void* A, long lda, const void* B, long ldb, int K, const SfGemmEpi& e, int c_dtype, void* stream);
 int sf_gemm_nt_256w4_launch(const void* A, long lda, const void* B, long ldb, int K, const SfGemmEpi& e, int c_dtype, void* stream);
 int sf_gemm_nt_128_launch(const void* A, long lda, const void* B, long ldb, int K, const SfGemmEpi& e, int c_dtype, void* stream);
-#ifdef SF_ABLATE
-// TOOLS BUILD ONLY (measured and rejected, round 6; DESIGN section 4 "Round 6"): the pair-resident 256 x 128 kernel -- two 4-wave workgroups
-// per CU so that one's epilogue runs under the other's K loop (tools/experiments/sf_gemm_p2.inc; tools/p2_ab.py).  SF_GEMM_P2=<bits> per call:
-// bit 0 = plain bf16, bit 1 = row-addend, bit 2 = fused d(SwiGLU); -1 from the launcher = the shape / epilogue does not qualify.
-#include "../../tools/experiments/sf_gemm_p2.inc"
-#endif
-// tools build only (-DSF_ABLATE): SF_GEMM_TILE=128 pins the 128x128 kernel
-static bool sf_gemm_use_256() {
-    static const bool use = sf_knob("SF_GEMM_TILE", 256) != 128;
-    return use;
-}
-
 #ifndef SF_EMU
 static int sf_gemm_cus() {
     static const int cus = [] {
@@ -152,49 +140,47 @@ static int sf_gemm_cus() {
 }
 #endif
 
+// "Chip-filling": more than half a 256 x 256 tile per CU and a long K.  Such shapes (every GEMM of the training step) take the 4-wave
+// software-pipelined kernel; smaller ones the 8-wave ping-pong kernel, whose prologue/epilogue is shorter.
+// (round 4: from MORE THAN HALF a tile per CU on -- 129 tiles; it was a whole tile per CU.  On grids of 144 ... 288 tiles the 4-wave
+//  kernel is 3 - 26 % faster than the ping-pong kernel at every K tried, profiles/r4_w4_small_ab.jsonl: DeepSeek-V3 dims at batch 1
+//  are 8 x 28 = 224 tiles and spent 30 % of their step in the ping-pong kernel.  Up to half a tile per CU: the 128 x 128 kernel or
+//  split-K, sf_gemm_dispatch.)
+static bool sf_gemm_chip_filling(long tiles, int K) {
+#ifdef SF_EMU   // interpreter build (tests): "chip-filling" means nothing there -- long-K shapes take the 4-wave kernel so that
+                // both 256-tile kernels are exercised by the CPU suite
+    (void)tiles;
+    return K >= 512;
+#else
+    return 2L * tiles > sf_gemm_cus() && K >= 512;
+#endif
+}
+
+// the plain epilogue: C = A . B^T, alpha 1, beta 0, no addend, no residual (the entry points set what differs)
+static SfGemmEpi sf_gemm_epi(void* C, long ldc, int M, int N) {
+    SfGemmEpi e;
+    e.C = C; e.ldc = ldc; e.R = nullptr; e.ldr = 0;
+    e.Cadd = nullptr; e.ldadd = 0; e.add_S = 1; e.add_Spad = 1; e.add_off = 0;
+    e.M = M; e.N = N; e.alpha = 1.0f; e.beta = 0.0f;
+    return e;
+}
+
 static int sf_gemm_dispatch(const void* A, long lda, const void* B, long ldb, int K, const SfGemmEpi& e, int c_dtype,
                             void* stream) {
     const int M = e.M, N = e.N;
-#ifdef SF_ABLATE
-    {
-        const int p2 = sf_knob("SF_GEMM_P2", 0);
-        if ((e.Cadd ? (p2 & 2) : (p2 & 1)) && !e.sw_gu && !e.sw_dgu && !e.red_part) {
-            const int st = sf_gemm_nt_p2_launch(A, lda, B, ldb, K, e, c_dtype, stream);
-            if (st != -1) return st;
-        }
-    }
-#endif
-    // chip-filling shapes (>= one 256x256 tile per CU, long K: every GEMM of the training step) take the 4-wave
-    // software-pipelined kernel; smaller ones the 8-wave ping-pong kernel, whose prologue/epilogue is shorter.
-    // (tools build: SF_GEMM_W4=0 pins the ping-pong kernel, =1 forces the 4-wave kernel for every 256-tile shape)
-    static const int w4_mode = sf_knob("SF_GEMM_W4", -1);
-#ifdef SF_EMU   // interpreter build (tests): "chip-filling" means nothing there -- long-K shapes take the 4-wave kernel so that
-                // both 256-tile kernels are exercised by the CPU suite
-    const bool big = K >= 512;
-#else
-    // (round 4: from MORE THAN HALF a tile per CU on -- 129 tiles; it was a whole tile per CU.  On grids of 144 ... 288 tiles the 4-wave
-    //  kernel is 3 - 26 % faster than the ping-pong kernel at every K tried, tools/w4_small_ab.py, profiles/r4_w4_small_ab.jsonl: DeepSeek-V3
-    //  dims at batch 1 are 8 x 28 = 224 tiles and spent 30 % of their step in the ping-pong kernel.  Up to half a tile per CU: the
-    //  128 x 128 kernel or split-K, below.)
-    const bool big = 2L * ((M + 255) / 256) * ((N + 255) / 256) > sf_gemm_cus() && K >= 512;
-#endif
+    const long tiles = (long)((M + 255) / 256) * ((N + 255) / 256);
+    const bool big = sf_gemm_chip_filling(tiles, K);
     const bool w4_ok = !(e.Cadd && e.alpha != 1.0f);   // its addend path starts the accumulators from Cadd
 #ifndef SF_EMU
     // Under-filled grids (round 4): with at most HALF as many 256 x 256 tiles as CUs -- the N = H GEMMs of a bs 1 x 4096 recipe at
     // H = 2048 are 16 x 8 = 128 tiles on 256 CUs -- the 128 x 128 kernel (4 x the workgroups, two per CU) keeps every CU busy and wins
     // by 8 ... 39 % (4096 x 2048 x {4096, 5120, 6144, 12288, 32000}, 2048 x 4096 x 4096); from 160 tiles up the 256-tile kernels are
-    // faster again (tools/small_tile_ab.py, profiles/r4_small_tile_ab.jsonl).
-    {
-        const int cus = sf_gemm_cus();
-        static const int small_tiles = sf_knob("SF_GEMM_SMALL128", 1);
-        if (small_tiles && 2L * ((M + 255) / 256) * ((N + 255) / 256) <= cus && sf_gemm_use_256())
-            return sf_gemm_nt_128_launch(A, lda, B, ldb, K, e, c_dtype, stream);
-    }
+    // faster again (profiles/r4_small_tile_ab.jsonl).
+    if (2L * tiles <= sf_gemm_cus()) return sf_gemm_nt_128_launch(A, lda, B, ldb, K, e, c_dtype, stream);
 #endif
-    if (K % 64 == 0 && K >= 64 && M >= 192 && N >= 192 && sf_gemm_use_256() && w4_ok &&
-        (w4_mode == 1 || (w4_mode < 0 && big)))
+    if (K % 64 == 0 && K >= 64 && M >= 192 && N >= 192 && w4_ok && big)
         return sf_gemm_nt_256w4_launch(A, lda, B, ldb, K, e, c_dtype, stream);
-    if (K % 64 == 0 && K >= 64 && M >= 192 && N >= 192 && sf_gemm_use_256())
+    if (K % 64 == 0 && K >= 64 && M >= 192 && N >= 192)
         return sf_gemm_nt_256_launch(A, lda, B, ldb, K, e, c_dtype, stream);
     return sf_gemm_nt_128_launch(A, lda, B, ldb, K, e, c_dtype, stream);
 }
@@ -240,14 +226,10 @@ extern "C" int sf_gemm_nt_ws(const void* A, long lda, const void* B, long ldb, v
                              const void* R, long ldr, float* workspace, long workspace_floats, void* stream) {
     if (int st = sf_gemm_check(lda, ldb, ldc, ldr, M, N, K, c_dtype, R)) return st;
     if (M == 0 || N == 0) return 0;
-    SfGemmEpi e;
-    e.C = C; e.ldc = ldc; e.R = (const sf_bf16*)R; e.ldr = ldr;
-    e.Cadd = nullptr; e.ldadd = 0; e.add_S = 1; e.add_Spad = 1; e.add_off = 0;
-    e.M = M; e.N = N; e.alpha = 1.0f; e.beta = 0.0f;
-    if (sf_gemm_use_256()) {
-        const int st = sf_gemm_nt_256w4_splitk_launch(A, lda, B, ldb, K, e, c_dtype, workspace, workspace_floats, stream);
-        if (st != -1) return st;
-    }
+    SfGemmEpi e = sf_gemm_epi(C, ldc, M, N);
+    e.R = (const sf_bf16*)R; e.ldr = ldr;
+    const int st = sf_gemm_nt_256w4_splitk_launch(A, lda, B, ldb, K, e, c_dtype, workspace, workspace_floats, stream);
+    if (st != -1) return st;
     return sf_gemm_dispatch(A, lda, B, ldb, K, e, c_dtype, stream);
 }
 
@@ -255,10 +237,9 @@ extern "C" int sf_gemm_nt(const void* A, long lda, const void* B, long ldb, void
                           int K, float alpha, float beta, const void* R, long ldr, void* stream) {
     if (int st = sf_gemm_check(lda, ldb, ldc, ldr, M, N, K, c_dtype, R)) return st;
     if (M == 0 || N == 0) return 0;
-    SfGemmEpi e;
-    e.C = C; e.ldc = ldc; e.R = (const sf_bf16*)R; e.ldr = ldr;
-    e.Cadd = nullptr; e.ldadd = 0; e.add_S = 1; e.add_Spad = 1; e.add_off = 0;
-    e.M = M; e.N = N; e.alpha = alpha; e.beta = beta;
+    SfGemmEpi e = sf_gemm_epi(C, ldc, M, N);
+    e.R = (const sf_bf16*)R; e.ldr = ldr;
+    e.alpha = alpha; e.beta = beta;
     return sf_gemm_dispatch(A, lda, B, ldb, K, e, c_dtype, stream);
 }
 
@@ -270,32 +251,14 @@ extern "C" int sf_gemm_nt_swiglu_bwd(const void* A, long lda, const void* B, lon
     SF_CHECK_ARG(gu && dgu && dact && ldgu % 8 == 0 && lddgu % 8 == 0 && lddact % 8 == 0 && I % 8 == 0,
                  "sf_gemm_nt_swiglu_bwd: gu / dgu / dact rows must be 16-byte aligned");
     if (M == 0 || I == 0) return 0;
-    SfGemmEpi e;
-    e.C = dact; e.ldc = lddact; e.R = nullptr; e.ldr = 0;
-    e.Cadd = nullptr; e.ldadd = 0; e.add_S = 1; e.add_Spad = 1; e.add_off = 0;
-    e.M = M; e.N = I; e.alpha = 1.f; e.beta = 0.f;
-#ifdef SF_EMU
-    const bool big = K >= 512;
-#else
-    const bool big = 2L * ((M + 255) / 256) * (I / 256) > sf_gemm_cus() && K >= 512;      // (more than half a tile per CU, as in sf_gemm_dispatch)
-#endif
-    static const int fuse = sf_knob("SF_GEMM_SWIGLU_FUSE", 1);
+    const SfGemmEpi e = sf_gemm_epi(dact, lddact, M, I);
+    const bool big = sf_gemm_chip_filling((long)((M + 255) / 256) * (I / 256), K);
     const bool aligned = ((size_t)gu & 15) == 0 && ((size_t)dgu & 15) == 0 && ((size_t)dact & 15) == 0;
-#ifdef SF_ABLATE
-    if (fuse && aligned && (sf_knob("SF_GEMM_P2", 0) & 4)) {
-        SfGemmEpi ef = e;
-        ef.sw_gu = (const sf_bf16*)gu; ef.sw_ldgu = ldgu;
-        ef.sw_dgu = (sf_bf16*)dgu; ef.sw_lddgu = lddgu;
-        const int st = sf_gemm_nt_p2_launch(A, lda, B, ldb, K, ef, SF_BF16, stream);
-        if (st != -1) return st;
-    }
-#endif
-    if (fuse && big && aligned && M >= 256 && I % 256 == 0 && K % 64 == 0 && sf_gemm_use_256()) {
-        // ragged M (real data: the collator pads a batch to its own longest sample): the whole 256-row tiles take the fused kernel,
-        // the last M % 256 rows the two steps -- same bits either way, so the split is invisible
-        // (M > 256, not whole tiles: ONE launch with the last row tile shifted up to end at row M -- GemmW4Args::mshift -- unless the
-        //  caller writes the gradients over gate|up; M < 256 never gets here)
-        const bool one = M % 256 == 0 || (M > 256 && (const void*)gu != (const void*)dgu && sf_knob("SF_GEMM_MSHIFT", 1));
+    if (big && aligned && M >= 256 && I % 256 == 0 && K % 64 == 0) {
+        // ragged M (real data: the collator pads a batch to its own longest sample): ONE launch with the last row tile shifted up to
+        // end at row M (GemmW4Args::mshift) -- unless the caller writes the gradients over gate|up: then the whole 256-row tiles take
+        // the fused kernel and the last M % 256 rows the two steps -- same bits either way, so the split is invisible
+        const bool one = M % 256 == 0 || (const void*)gu != (const void*)dgu;
         const int Mf = one ? M : M / 256 * 256, Mt = M - Mf;
         SfGemmEpi ef = e;
         ef.M = Mf;
@@ -315,39 +278,21 @@ extern "C" int sf_gemm_nt_swiglu_bwd(const void* A, long lda, const void* B, lon
 }
 
 // gu = A . Wgu^T (the fused gate|up projection, [M, 2I]) and act = round(silu(gate)) * up in ONE launch when the 4-wave kernel
-// can take the shape (whole tiles; see ADD = 3 in sf_gemm256w4_kernel.h); every other shape: the GEMM, then sf_swiglu_fwd.
+// can take the shape (whole column tiles; see ADD = 3 in sf_gemm256w4_kernel.h); every other shape: the GEMM, then sf_swiglu_fwd.
 extern "C" int sf_gemm_nt_swiglu_fwd(const void* A, long lda, const void* Wgu, long ldw, int M, int I, int K, void* gu, long ldgu,
                                      void* act, long ldact, void* stream) {
     SF_CHECK_ARG(I >= 0 && I < (1 << 29), "sf_gemm_nt_swiglu_fwd: bad I");
     if (int st = sf_gemm_check(lda, ldw, ldgu, 0, M, 2 * I, K, SF_BF16, nullptr)) return st;
     SF_CHECK_ARG(gu && act && ldgu % 8 == 0 && ldact % 8 == 0 && I % 8 == 0, "sf_gemm_nt_swiglu_fwd: gu / act rows must be 16-byte aligned");
     if (M == 0 || I == 0) return 0;
-    SfGemmEpi e;
-    e.C = gu; e.ldc = ldgu; e.R = nullptr; e.ldr = 0;
-    e.Cadd = nullptr; e.ldadd = 0; e.add_S = 1; e.add_Spad = 1; e.add_off = 0;
-    e.M = M; e.N = 2 * I; e.alpha = 1.f; e.beta = 0.f;
-#ifdef SF_EMU
-    const bool big = K >= 512;
-#else
-    const bool big = 2L * ((M + 255) / 256) * (I / 128) > sf_gemm_cus() && K >= 512;
-#endif
-    static const int fuse = sf_knob("SF_GEMM_SWIGLU_FWD_FUSE", 1);
+    SfGemmEpi e = sf_gemm_epi(gu, ldgu, M, 2 * I);
+    const bool big = sf_gemm_chip_filling((long)((M + 255) / 256) * (I / 128), K);
     const bool aligned = ((size_t)gu & 15) == 0 && ((size_t)act & 15) == 0;
-    if (fuse && big && aligned && M >= 256 && I % 128 == 0 && K % 64 == 0 && (I + 256L) * ldw * 2 < (1L << 31) && sf_gemm_use_256()) {
+    if (big && aligned && M >= 256 && I % 128 == 0 && K % 64 == 0 && (I + 256L) * ldw * 2 < (1L << 31)) {
         // ragged M: one launch with the last row tile shifted up to end at row M (GemmW4Args::mshift; the rows two tiles share get the
-        // same bits twice); with the knob off: whole tiles fused, the tail rows in two steps (same bits)
-        const bool one = M % 256 == 0 || (M > 256 && sf_knob("SF_GEMM_MSHIFT", 1));
-        const int Mf = one ? M : M / 256 * 256, Mt = M - Mf;
-        SfGemmEpi ef = e;
-        ef.M = Mf;
-        ef.sw_dgu = (sf_bf16*)act; ef.sw_lddgu = ldact;   // (sw_gu stays null: that is what selects the forward form)
-        if (int st = sf_gemm_nt_256w4_launch(A, lda, Wgu, ldw, K, ef, SF_BF16, stream)) return st;
-        if (Mt == 0) return 0;
-        SfGemmEpi et = e;
-        et.M = Mt;
-        et.C = (sf_bf16*)gu + (long)Mf * ldgu;
-        if (int st = sf_gemm_dispatch((const sf_bf16*)A + (long)Mf * lda, lda, Wgu, ldw, K, et, SF_BF16, stream)) return st;
-        return sf_swiglu_fwd(et.C, SF_BF16, ldgu, Mt, I, (sf_bf16*)act + (long)Mf * ldact, ldact, stream);
+        // same bits twice)
+        e.sw_dgu = (sf_bf16*)act; e.sw_lddgu = ldact;   // (sw_gu stays null: that is what selects the forward form)
+        return sf_gemm_nt_256w4_launch(A, lda, Wgu, ldw, K, e, SF_BF16, stream);
     }
     if (int st = sf_gemm_dispatch(A, lda, Wgu, ldw, K, e, SF_BF16, stream)) return st;
     return sf_swiglu_fwd(gu, SF_BF16, ldgu, M, I, act, ldact, stream);
@@ -358,15 +303,15 @@ extern "C" int sf_gemm_nt_swiglu_fwd(const void* A, long lda, const void* Wgu, l
 // roundup(Vd, 256) columns are stored; every later 128-column block of a row leaves as one {max, sum exp, argmax column, 0} record
 // in `part` (*nparts_out blocks, row-major: block q of row r at part[(r * part_stride + q) * 4]).  Otherwise all Vt columns are stored and *nparts_out = 0.  z must have room for Vt columns.
 // 1 when sf_gemm_nt_teacher (given `part`) takes the reduced form for this shape -- then z only needs roundup(Vd, 256) columns
+// (the teacher head's own size rule: 256 tiles or more, whatever the CU count -- not sf_gemm_chip_filling)
 extern "C" int sf_gemm_nt_teacher_reduces(int M, int Vt, int K, int Vd) {
 #ifdef SF_EMU
     const bool big = K >= 512;
 #else
     const bool big = (long)((M + 255) / 256) * ((Vt + 255) / 256) >= 256 && K >= 512;
 #endif
-    static const int fuse = sf_knob("SF_GEMM_TEACHER_FUSE", 1);
     const int vz = (Vd + 255) / 256 * 256;
-    return (fuse && big && Vd > 0 && vz < Vt && K % 64 == 0 && M >= 192 && sf_gemm_use_256()) ? 1 : 0;
+    return (big && Vd > 0 && vz < Vt && K % 64 == 0 && M >= 192) ? 1 : 0;
 }
 
 extern "C" int sf_gemm_nt_teacher(const void* A, long lda, const void* Wp, long ldw, int M, int Vt, int K, int Vd, void* z, long ldz,
@@ -379,18 +324,9 @@ extern "C" int sf_gemm_nt_teacher(const void* A, long lda, const void* Wp, long 
     *vz_out = Vt;
     *nparts_out = 0;
     if (M == 0) return 0;
-    SfGemmEpi e;
-    e.C = z; e.ldc = ldz; e.R = nullptr; e.ldr = 0;
-    e.Cadd = nullptr; e.ldadd = 0; e.add_S = 1; e.add_Spad = 1; e.add_off = 0;
-    e.M = M; e.N = Vt; e.alpha = 1.f; e.beta = 0.f;
-#ifdef SF_EMU
-    const bool big = K >= 512;
-#else
-    const bool big = (long)((M + 255) / 256) * ((Vt + 255) / 256) >= 256 && K >= 512;
-#endif
-    const int vz = (Vd + 255) / 256 * 256;
-    (void)big;
+    SfGemmEpi e = sf_gemm_epi(z, ldz, M, Vt);
     if (will_reduce) {
+        const int vz = (Vd + 255) / 256 * 256;
         e.red_part = part; e.red_stride = part_stride; e.red_n0 = vz;
         *vz_out = vz;
         *nparts_out = (Vt - vz + 127) / 128;
@@ -406,11 +342,10 @@ extern "C" int sf_gemm_nt_rowadd(const void* A, long lda, const void* B, long ld
     SF_CHECK_ARG(Cadd && ldadd % 4 == 0 && S > 0 && Spad >= S && off >= 0 && off + S <= Spad && M % S == 0,
                  "sf_gemm_nt_rowadd: bad addend layout");
     if (M == 0 || N == 0) return 0;
-    SfGemmEpi e;
-    e.C = C; e.ldc = ldc; e.R = nullptr; e.ldr = 0;
+    SfGemmEpi e = sf_gemm_epi(C, ldc, M, N);
     e.Cadd = Cadd; e.ldadd = ldadd; e.add_S = S; e.add_Spad = Spad; e.add_off = off;
-    e.M = M; e.N = N; e.alpha = alpha; e.beta = 0.f;
-    if (workspace && sf_gemm_use_256()) {       // under-filled grid (batch-1 recipes): split-K, the addend joins in the reduce (sf_gemm_nt_ws)
+    e.alpha = alpha;
+    if (workspace) {       // under-filled grid (batch-1 recipes): split-K, the addend joins in the reduce (sf_gemm_nt_ws)
         const int st = sf_gemm_nt_256w4_splitk_launch(A, lda, B, ldb, K, e, c_dtype, workspace, workspace_floats, stream);
         if (st != -1) return st;
     }

@@ -46,20 +46,18 @@ struct Gemm256Args {
     int M, N, K;
     int tiles_m, tiles_n;
     int gm;     // tile-rows per L2 group of the XCD-aware tile order
-    int flags;  // tuning experiments: bit0 = no s_setprio around the MFMA segment
+    int flags;  // bit0 = no s_setprio around the MFMA segment; always 0
 };
 
 #ifdef SF_EMU
 SF_DEVICE void raw_barrier() { sfemu::block_barrier(); }
 SF_DEVICE void wait_lgkm0() {}
 SF_DEVICE void wait_vm4() {}
-SF_DEVICE void wait_vm8() {}
 SF_DEVICE void sched_fence() {}
 #else
 SF_DEVICE void raw_barrier() { __builtin_amdgcn_s_barrier(); }
 SF_DEVICE void wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 SF_DEVICE void wait_vm4() { asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); }
-SF_DEVICE void wait_vm8() { asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); }
 SF_DEVICE void sched_fence() { __builtin_amdgcn_sched_barrier(0); }
 #endif
 
@@ -203,26 +201,7 @@ SF_GLOBAL void SF_LAUNCH_BOUNDS(512, 2) gemm_nt_256_kernel(Gemm256Args p) {
         }
 }
 
-
-#ifdef SF_ABLATE
-#include "../../tools/experiments/sf_gemm256_variants.inc"
-#endif
-
 }  // namespace
-
-#ifdef SF_EMU
-#define SF_ALLOW_SMEM2(kernel)
-#else
-#define SF_ALLOW_SMEM2(kernel)                                                                                   \
-    do {                                                                                                         \
-        static bool done_ = false;                                                                               \
-        if (!done_) {                                                                                            \
-            hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kBufBytes); \
-            (void)hipGetLastError();                                                                             \
-            done_ = true;                                                                                        \
-        }                                                                                                        \
-    } while (0)
-#endif
 
 // launched by sf_gemm_nt (sf_gemm.hip) when the shape qualifies
 int sf_gemm_nt_256_launch(const void* A, long lda, const void* B, long ldb, int K, const SfGemmEpi& e, int c_dtype,
@@ -235,47 +214,16 @@ int sf_gemm_nt_256_launch(const void* A, long lda, const void* B, long ldb, int 
     p.M = M; p.N = N; p.K = K;
     p.tiles_m = (M + TM - 1) / TM;
     p.tiles_n = (N + TN - 1) / TN;
-    p.gm = sf_knob("SF_GEMM_GM", 4);
-    if (p.gm < 1) p.gm = 1;
-    p.flags = sf_knob("SF_GEMM_FLAGS", 0);
+    p.gm = 4;      // (a product constant kept as a kernel argument: DESIGN section 7)
+    p.flags = 0;   // (likewise)
     const long nblk = (long)p.tiles_m * p.tiles_n;
 #ifndef SF_EMU
     static bool attr_set = false;
     if (!attr_set) {  // 128 KiB of dynamic LDS needs the opt-in
         hipFuncSetAttribute((const void*)gemm_nt_256_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kBufBytes);
         hipFuncSetAttribute((const void*)gemm_nt_256_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kBufBytes);
-#ifdef SF_ABLATE
-        hipFuncSetAttribute((const void*)gemm_nt_256_mf32_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kBufBytes);
-        hipFuncSetAttribute((const void*)gemm_nt_256_mf32_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kBufBytes);
-#endif
         (void)hipGetLastError();
         attr_set = true;
-    }
-#endif
-#ifdef SF_ABLATE   // A/B variants, tools only (tools/experiments/sf_gemm256_variants.inc)
-    static const int variant = [] { const char* e = getenv("SF_GEMM_VARIANT"); return e ? atoi(e) : 0; }();
-    if (variant >= 1) {
-#define SF_V2_CASE(V)                                                                                                    \
-    case V:                                                                                                              \
-        SF_ALLOW_SMEM2((gemm_nt_256v2_kernel<0, V - 1>));                                                                \
-        SF_ALLOW_SMEM2((gemm_nt_256v2_kernel<1, V - 1>));                                                                \
-        if (c_dtype == SF_F32) SF_LAUNCH((gemm_nt_256v2_kernel<1, V - 1>), dim3((unsigned)nblk), dim3(512), 2 * kBufBytes, stream, p); \
-        else SF_LAUNCH((gemm_nt_256v2_kernel<0, V - 1>), dim3((unsigned)nblk), dim3(512), 2 * kBufBytes, stream, p);     \
-        break;
-        switch (variant) {
-            SF_V2_CASE(1) SF_V2_CASE(2) SF_V2_CASE(3) SF_V2_CASE(5) SF_V2_CASE(7) SF_V2_CASE(9) SF_V2_CASE(13) SF_V2_CASE(15)
-            default: SF_CHECK_ARG(false, "unknown SF_GEMM_VARIANT");
-        }
-#undef SF_V2_CASE
-        return sf_check_launch("sf_gemm_nt(256v2)");
-    }
-    static const bool mf32 = [] { const char* e = getenv("SF_GEMM_MFMA"); return e ? atoi(e) == 32 : false; }();
-    if (mf32) {
-        if (c_dtype == SF_F32)
-            SF_LAUNCH((gemm_nt_256_mf32_kernel<1>), dim3((unsigned)nblk), dim3(512), 2 * kBufBytes, stream, p);
-        else
-            SF_LAUNCH((gemm_nt_256_mf32_kernel<0>), dim3((unsigned)nblk), dim3(512), 2 * kBufBytes, stream, p);
-        return sf_check_launch("sf_gemm_nt(256 mf32)");
     }
 #endif
     if (c_dtype == SF_F32)

@@ -8,7 +8,7 @@
 // kernels needed: 70 transposes / 48 GB of traffic per training step at cfg 2.
 //
 // Same pipeline as sf_gemm256w4.hip (4 waves x 128x128, one wave per SIMD, fragments double-buffered in
-// registers, LDS-DMA threaded between the MFMAs, one barrier per K-tile).  What differs is the LDS image and the
+// registers, LDS-DMA threaded between the MFMAs).  What differs is the LDS image and the
 // fragment reads:
 //   * a K-tile of an operand is staged as two half-tiles of 128 columns: [64 k][256 B], i.e. rows of the
 //     SOURCE matrix land as rows of LDS (an LDS-DMA instruction moves 4 k-rows x 256 B);
@@ -69,141 +69,8 @@ SF_DEVICE void tn_tile_coords(int bid, int nblk, int tiles_m, int tiles_n, int G
     tn = in_g / gsize;
 }
 
-#ifdef SF_ABLATE   // round-1 schedule (one barrier per K-tile, vmcnt(0)): tools build only, SF_GEMM_TN_PLAN=-1
-template <int OUT_F32, int SPREAD = 0>
-SF_GLOBAL void SF_LAUNCH_BOUNDS(256, 1) gemm_tn_256w4_kernel(GemmTnArgs p) {
-    SF_DYN_SMEM(smem);
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = sf_wave_id();
-    const int wr = wave >> 1, wc = wave & 1;
-    int tm, tn;
-    tn_tile_coords((int)blockIdx.x, (int)gridDim.x, p.tiles_m, p.tiles_n, p.gm, tm, tn);
-    const int m0 = tm * TM, n0 = tn * TN;
-    const int nkt = p.K / TK / p.ksplit;
-    const long k0 = (long)blockIdx.y * nkt * TK;      // first contraction row of this split
-    if (p.ksplit > 1) {                               // partial sums go to the fp32 workspace, plain store
-        p.e.C = p.ws + (long)blockIdx.y * p.M * p.N;
-        p.e.ldc = p.N;
-        p.e.alpha = 1.f;
-        p.e.beta = 0.f;
-    }
-
-    // ---- DMA sources: half hh (0,1 = A columns m0+0.., m0+128..; 2,3 = B) is 16 pieces of 4 k-rows x 256 B; this wave
-    // stages pieces 4*wave .. 4*wave+3 of every half.  Lane: k-row skr = lane>>4 of the piece, physical chunk lane&15.
-    const int skr = lane >> 4;
-    const sf_bf16* src[16];
-#pragma unroll
-    for (int hh = 0; hh < 4; ++hh)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int krow = (4 * wave + j) * 4 + skr;
-            const int hk = (krow & 3) | (((krow >> 3) & 1) << 2);
-            const int lc = (lane & 15) ^ (hk << 1);            // logical 16-byte chunk fetched into physical chunk lane&15
-            const bool isA = hh < 2;
-            const int dim = isA ? p.M : p.N;
-            int col = (isA ? m0 : n0) + (hh & 1) * 128 + lc * 8;
-            col = col + 8 <= dim ? col : dim - 8;
-            src[hh * 4 + j] = (isA ? p.A + (k0 + krow) * p.lda : p.B + (k0 + krow) * p.ldb) + col;
-        }
-    const long incA = (long)TK * p.lda, incB = (long)TK * p.ldb;
-    auto dma = [&](int g, int kt) {  // g = hh*4 + j: piece 4*wave+j of half hh of the next un-issued K-tile
-        char* dst = smem + (kt & 1) * kBufBytes + (g >> 2) * kHalfBytes + (4 * wave + (g & 3)) * 1024;
-        sf_glds16_opaque(src[g], dst);
-        src[g] += (g < 8) ? incA : incB;
-    };
-
-    // ---- fragment reads (transposed): lane constants of ds_read_b64_tr_b16 into the [64 k][256 B] image
-    const int fi = lane & 15, fg = lane >> 4;
-    const int fh = (fi >> 2) | ((fg & 1) << 2);
-    const int frag_lane = (8 * fg + (fi >> 2)) * 256 + ((fi >> 1) & 1) * 16 + (fi & 1) * 8;
-    const int a_half = wr * kHalfBytes, b_half = (2 + wc) * kHalfBytes;
-
-    sf_v4f acc[8][8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[i][j] = sf_v4f{0.f, 0.f, 0.f, 0.f};
-    sf_v8s f[2][16];  // [set][0..7 = B n-tiles, 8..15 = A m-tiles]
-
-    auto read_frag = [&](int set, int g, const char* buf, int ks) {
-        const char* a = buf + (g < 8 ? b_half : a_half) + ks * (32 * 256) + frag_lane + ((((g & 7)) ^ fh) << 5);
-        const sf_v4s lo = sf_ds_read_tr16(a);
-        const sf_v4s up = sf_ds_read_tr16(a + 4 * 256);
-        f[set][g] = sf_v8s{lo[0], lo[1], lo[2], lo[3], up[0], up[1], up[2], up[3]};
-    };
-
-    // ---- prologue
-#pragma unroll
-    for (int g = 0; g < 16; ++g) dma(g, 0);
-    if (nkt > 1) {
-#pragma unroll
-        for (int g = 0; g < 16; ++g) dma(g, 1);
-    }
-    tn_wait_all();
-    tn_barrier();
-#pragma unroll
-    for (int g = 0; g < 16; ++g) read_frag(0, g, smem, 0);
-
-    auto tile = [&](auto READ_NEXT, auto DO_DMA, int t) {
-        const char* cur = smem + (t & 1) * kBufBytes;
-        const char* nxt = smem + ((t + 1) & 1) * kBufBytes;
-        // ---- half-step 2t: compute set 0; fragments of k-half 1 -> set 1 (front-loaded)
-#pragma unroll
-        for (int g = 0; g < 16; ++g) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int idx = g * 4 + q, mt = idx >> 3, nt = idx & 7;
-                sf_mfma16_acc(f[0][nt], f[0][8 + mt], acc[mt][nt]);
-            }
-            tn_fence();
-            if (SPREAD) read_frag(1, g, cur, 1);
-            else if (g < 8) { read_frag(1, 2 * g, cur, 1); read_frag(1, 2 * g + 1, cur, 1); }
-            tn_fence();
-        }
-        tn_wait_all();   // my pieces of tile t+1 have landed; my reads of buffer t&1 have returned
-        tn_barrier();    // -> tile t+1 visible to everyone, buffer t&1 free for tile t+2
-        // ---- half-step 2t+1: compute set 1; fragments of (t+1, k-half 0) -> set 0; stage tile t+2
-#pragma unroll
-        for (int g = 0; g < 16; ++g) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int idx = g * 4 + q, mt = idx >> 3, nt = idx & 7;
-                sf_mfma16_acc(f[1][nt], f[1][8 + mt], acc[mt][nt]);
-            }
-            tn_fence();
-            if constexpr (decltype(READ_NEXT)::value) {
-                if (SPREAD) read_frag(0, g, nxt, 0);
-                else if (g < 4) { read_frag(0, 2 * g, nxt, 0); read_frag(0, 2 * g + 1, nxt, 0); }
-                else if (g < 12) read_frag(0, g + 4, nxt, 0);
-            }
-            if constexpr (decltype(DO_DMA)::value) dma(g, t + 2);
-            tn_fence();
-        }
-    };
-
-    int t = 0;
-    for (; t + 2 < nkt; ++t) tile(std::true_type{}, std::true_type{}, t);
-    if (t + 1 < nkt) { tile(std::true_type{}, std::false_type{}, t); ++t; }
-    tile(std::false_type{}, std::false_type{}, t);
-
-    // ---- epilogue: lane owns C[m][n..n+3]
-    sf_mfma_drain();
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) sf_acc_touch(acc[i][j]);
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-            sf_gemm_store4<OUT_F32, 0>(p.e, m0 + wr * 128 + i * 16 + (lane & 15), n0 + wc * 128 + j * 16 + 4 * (lane >> 4), v);
-        }
-}
-
-#endif
-
 // ---------------------------------------------------------------------------------------------------------------
-// Round 2: the same kernel under the plan-scheduled main loop of sf_gemm256w4_kernel.h -- every non-MFMA instruction in
+// The plan-scheduled main loop of sf_gemm256w4_kernel.h (round 2) -- every non-MFMA instruction in
 // its own MFMA slot, the two operands' LDS halves released separately (3 barriers), counted vmcnt(16), DMA lead 1.1-1.6
 // iterations, buffer-descriptor LDS-DMA from inline asm with the K advance on the descriptor base (a scalar 64-bit add
 // per operand and K-tile; the per-lane offsets are loop constants).  A K-tile here carries 64 transposed fragment reads
@@ -543,8 +410,7 @@ extern "C" int sf_gemm_tn(const void* A, long lda, const void* B, long ldb, void
     p.M = M; p.N = N; p.K = K;
     p.tiles_m = (M + TM - 1) / TM;
     p.tiles_n = (N + TN - 1) / TN;
-    p.gm = sf_knob("SF_GEMM_GM", 4);
-    if (p.gm < 1) p.gm = 1;
+    p.gm = 4;   // (a product constant kept as a kernel argument: DESIGN section 7)
     SF_CHECK_ARG(ksplit == 0 || ksplit == 1 || ksplit == 2, "sf_gemm_tn: ksplit must be 0 (automatic), 1 (never) or 2 (two-way)");
     const long nblk = (long)p.tiles_m * p.tiles_n;
     SF_CHECK_ARG(nblk < (1L << 31), "sf_gemm_tn: grid too large");
@@ -562,14 +428,13 @@ extern "C" int sf_gemm_tn(const void* A, long lda, const void* B, long ldb, void
     }
     // pace-keeping counters: the last kTnSyncFloats floats of the workspace (when it is large enough), zeroed per launch
     p.sync = nullptr;
-    p.sync_every = sf_knob("SF_GEMM_TN_SYNC", 128);
+    p.sync_every = 128;   // (a product constant kept as a kernel argument: DESIGN section 7)
 #ifndef SF_EMU
     {
         const long need = (p.ksplit > 1 ? 2L * M * N : 0L) + kTnSyncFloats;
-        const bool pow2 = p.sync_every >= 16 && (p.sync_every & (p.sync_every - 1)) == 0;
         // counters used = 8 XCDs x groups per XCD (tn_pace_group): they must fit the tail (a grid of > ~130 k tiles would not)
         const long groups_per_xcd = ((long)p.ksplit * (nblk / 8 + 1) + 31) / 32;
-        if (workspace && workspace_floats >= need && pow2 && K / TK / p.ksplit >= 2 * p.sync_every && nblk >= 64 &&
+        if (workspace && workspace_floats >= need && K / TK / p.ksplit >= 2 * p.sync_every && nblk >= 64 &&
             (p.ksplit == 1 || nblk % 8 == 0) && 8 * groups_per_xcd <= kTnSyncFloats) {
             p.sync = reinterpret_cast<unsigned*>(workspace + workspace_floats - kTnSyncFloats);
             if (hipMemsetAsync(p.sync, 0, kTnSyncFloats * sizeof(float), (hipStream_t)stream) != hipSuccess) p.sync = nullptr;
@@ -578,8 +443,8 @@ extern "C" int sf_gemm_tn(const void* A, long lda, const void* B, long ldb, void
 #endif
     // plan: which operand's LDS halves are released / re-staged first (0 = B, 1 = A).  Measured on the step's shapes
     // (profiles/old/r2_gemm_tn_ab.jsonl): A first wins for wide X (down-proj, N = 14336), B first elsewhere; both beat the
-    // round-1 schedule (tools build: SF_GEMM_TN_PLAN=-1) by 3-8 %.
-    const int plan = sf_knob("SF_GEMM_TN_PLAN", N > 8192 ? 1 : 0);
+    // round-1 schedule (one barrier per K-tile, vmcnt(0); in this file's history) by 3-8 %.
+    const int plan = N > 8192 ? 1 : 0;
     const bool f32_main = p.ksplit > 1 || c_dtype == SF_F32;
     const dim3 grid((unsigned)nblk, (unsigned)p.ksplit);
 #define SF_TN_CASE(F32, AF)                                                                                           \
@@ -590,17 +455,7 @@ extern "C" int sf_gemm_tn(const void* A, long lda, const void* B, long ldb, void
     SF_TN_CASE(0, 0) SF_TN_CASE(1, 0) SF_TN_CASE(0, 1) SF_TN_CASE(1, 1)
 #undef SF_TN_CASE
     {
-#ifdef SF_ABLATE
-        if (f32_main) {
-            SF_TN_SMEM((gemm_tn_256w4_kernel<1>));
-            SF_LAUNCH((gemm_tn_256w4_kernel<1>), grid, dim3(256), 2 * kBufBytes, stream, p);
-        } else {
-            SF_TN_SMEM((gemm_tn_256w4_kernel<0>));
-            SF_LAUNCH((gemm_tn_256w4_kernel<0>), grid, dim3(256), 2 * kBufBytes, stream, p);
-        }
-#else
         SF_CHECK_ARG(false, "sf_gemm_tn: no kernel for this configuration");
-#endif
     }
     if (p.ksplit > 1) {
         const long units = (long)M * (N / 4);

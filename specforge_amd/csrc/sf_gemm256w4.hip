@@ -18,17 +18,16 @@ int sf_gemm_nt_256w4_launch(const void* A, long lda, const void* B, long ldb, in
     // tiles at a time, so GM sets how many A / B panels its L2 holds at once).  A per-shape choice was measured and rejected
     // (round 3): on one box GM = 1 gained 3-4 % on narrow-N / mid-K shapes and 8 gained 0.5-0.9 % on wide N, on the next box the
     // same sweep showed nothing, and in-step the per-shape table was 0.3 ms SLOWER than 4 everywhere (profiles/old/r3_gemm_gm_ab.jsonl).
-    p.gm = sf_knob("SF_GEMM_GM", 4);
-    if (p.gm < 1) p.gm = 1;
+    p.gm = 4;   // (a product constant kept as a kernel argument: DESIGN section 7)
     long nblk = (long)p.tiles_m * p.tiles_n;
     // The last, partly filled round of the persistent walk: lm_head forward (16384 x 32000: 8000 tiles) leaves 64 tiles for a 32nd
     // round on 256 CUs -- 192 CUs idle for a whole tile time (2.3 % of the launch).  When the remainder is a whole number of
     // COLUMN tiles and small (<= a quarter of the CUs), those columns are peeled off: the persistent kernel walks an exact number of
     // rounds and the peeled columns run as 128 x 128 tiles (4 x the workgroups, a quarter of the work each: one short round of the
-    // generic kernel, measured 0.050 ms against the 0.098 ms round it replaces; tools/tail_bench.py).
+    // generic kernel, measured 0.050 ms against the 0.098 ms round it replaces).
     // (round 4: the row-addend form too -- at small M its grids are the ones that leave such rounds: 4096 x 5120, cfg 4 at bs 1 x 4096,
     // is 320 tiles = 1 round + 64; 2048 x 9216, DeepSeek-V3 dims at bs 1 x 2048, 288 = 1 + 32.  The addend's columns move with C's.)
-    if (!p.e.sw_gu && !p.e.sw_dgu && !p.e.red_part && sf_knob("SF_GEMM_PEEL", 1)) {
+    if (!p.e.sw_gu && !p.e.sw_dgu && !p.e.red_part) {
         const long cus = sf_w4_grid(1L << 30);
         const long rem = nblk % cus;
         if (nblk > cus && rem != 0 && rem * 4 <= cus && rem % p.tiles_m == 0 && rem / p.tiles_m < p.tiles_n) {
@@ -48,8 +47,8 @@ int sf_gemm_nt_256w4_launch(const void* A, long lda, const void* B, long ldb, in
     }
     // ragged M: the last row tile is shifted up to end at row M (GemmW4Args::mshift) unless the epilogue reads what it writes
     p.mshift = (M > TM && M % TM != 0 && p.e.beta == 0.f && (const void*)p.e.R != (const void*)p.e.C &&
-                (!p.e.sw_gu || (const void*)p.e.sw_gu != (const void*)p.e.sw_dgu) && sf_knob("SF_GEMM_MSHIFT", 1)) ? 1 : 0;
-    p.epi_direct = sf_knob("SF_GEMM_EPI_DIRECT", 1);
+                (!p.e.sw_gu || (const void*)p.e.sw_gu != (const void*)p.e.sw_dgu)) ? 1 : 0;
+    p.epi_direct = 1;   // (a product constant kept as a kernel argument: DESIGN section 7)
     // the 32-bit per-lane byte offsets of the buffer-descriptor DMA cover one 256-row tile of either operand
     SF_CHECK_ARG(256L * lda * 2 < (1L << 31) && 256L * ldb * 2 < (1L << 31), "sf_gemm_nt: row stride too large for the 256-tile kernel");
     if (p.e.Cadd) SF_CHECK_ARG(p.e.alpha == 1.0f, "sf_gemm_nt_rowadd: the 4-wave kernel needs alpha == 1");
@@ -63,54 +62,15 @@ int sf_gemm_nt_256w4_launch(const void* A, long lda, const void* B, long ldb, in
     SF_CHECK_ARG(add != 2 || (!f32 && (M % TM == 0 || p.mshift) && N % TN == 0 && p.e.alpha == 1.f && p.e.beta == 0.f && !p.e.R),
                  "sf_gemm_nt_swiglu_bwd: the fused form takes whole bf16 tiles only");
     // which operand's LDS half is released and re-staged first: B for narrow N, A for wide N (measured, see the header)
-    int sched = N <= 8192 ? 12 : 13;
+    const int sched = N <= 8192 ? 12 : 13;
 #define SF_W4_CASE(F32, ADD, SCHED) \
     if (f32 == F32 && add == ADD && sched == SCHED) return sf_w4_launch_##F32##_##ADD##_##SCHED(p, nblk, stream);
-#define SF_W4_LOCAL(F32, ADD, SCHED)                                                                                      \
-    if (f32 == F32 && add == ADD && sched == SCHED) {                                                                    \
-        SF_W4_SMEM((gemm_nt_256w4_kernel<F32, ADD, SCHED>), w4_smem_bytes<ADD>());                                       \
-        SF_LAUNCH((gemm_nt_256w4_kernel<F32, ADD, SCHED>), dim3(sf_w4_grid(nblk, ADD == 1)), dim3(256), w4_smem_bytes<ADD>(), stream, p);   \
-        return sf_check_launch("sf_gemm_nt(256w4 tools)");                                                               \
-    }
-#ifdef SF_ABLATE   // A/B variants, tools only (tools/experiments/sf_gemm256w4_*.inc)
-    p.cyc = sf_knob("SF_GEMM_CYC", 0);
-    p.stagger = sf_knob("SF_GEMM_STAGGER", 0);
-    {
-        const int ks = sf_knob("SF_GEMM_SCHED", -1);
-        if (ks >= 0) {
-            SF_CHECK_ARG(!f32 && !add, "SF_GEMM_SCHED: plain bf16 output only (A/B knob)");
-            sched = ks;
-            SF_W4_LOCAL(0, 0, 0) SF_W4_LOCAL(0, 0, 2) SF_W4_LOCAL(0, 0, 3) SF_W4_LOCAL(0, 0, 5) SF_W4_LOCAL(0, 0, 9) SF_W4_LOCAL(0, 0, 11)
-        }
-        const int abl = sf_knob("SF_GEMM_ABL", 0);
-#define SF_ABL_CASE(V)                                                                                                    \
-    if (abl == V) {                                                                                                      \
-        SF_W4_SMEM((gemm_nt_256w4_kernel<0, 0, 0, V>));                                                                  \
-        SF_LAUNCH((gemm_nt_256w4_kernel<0, 0, 0, V>), dim3(sf_w4_grid(nblk)), dim3(256), kW4SmemBytes, stream, p);        \
-        return sf_check_launch("abl");                                                                                   \
-    }
-        SF_ABL_CASE(1) SF_ABL_CASE(2) SF_ABL_CASE(3) SF_ABL_CASE(8) SF_ABL_CASE(16)
-#undef SF_ABL_CASE
-        // the same decomposition for the product plan (B first): SF_GEMM_ABL12 = 1 no reads | 2 no DMA | 4 no barriers | 8 no waits
-        const int abl12 = sf_knob("SF_GEMM_ABL12", 0);
-#define SF_ABL12_CASE(V)                                                                                                  \
-    if (abl12 == V) {                                                                                                    \
-        SF_W4_SMEM((gemm_nt_256w4_kernel<0, 0, 12, V>));                                                                 \
-        SF_LAUNCH((gemm_nt_256w4_kernel<0, 0, 12, V>), dim3(sf_w4_grid(nblk)), dim3(256), kW4SmemBytes, stream, p);       \
-        return sf_check_launch("abl12");                                                                                 \
-    }
-        SF_ABL12_CASE(1) SF_ABL12_CASE(2) SF_ABL12_CASE(4) SF_ABL12_CASE(8) SF_ABL12_CASE(12) SF_ABL12_CASE(14) SF_ABL12_CASE(15)
-#undef SF_ABL12_CASE
-    }
-    if (int st = sf_gemm_nt_256w4_variants_launch(p, nblk, c_dtype, stream); st != -1) return st;
-#endif
     SF_W4_CASE(0, 0, 12) SF_W4_CASE(0, 0, 13) SF_W4_CASE(1, 0, 12) SF_W4_CASE(1, 0, 13)
     SF_W4_CASE(0, 1, 12) SF_W4_CASE(0, 1, 13) SF_W4_CASE(1, 1, 12) SF_W4_CASE(1, 1, 13)
     SF_W4_CASE(0, 2, 12) SF_W4_CASE(0, 2, 13)
     SF_W4_CASE(0, 3, 12) SF_W4_CASE(0, 3, 13)
     SF_W4_CASE(0, 4, 12) SF_W4_CASE(0, 4, 13)
 #undef SF_W4_CASE
-#undef SF_W4_LOCAL
     SF_CHECK_ARG(false, "sf_gemm_nt(256w4): no kernel for this configuration");
 }
 
@@ -198,9 +158,6 @@ int sf_gemm_nt_256w4_splitk_launch(const void* A, long lda, const void* B, long 
     p.tiles_m = tiles_m; p.tiles_n = N / TN;
     p.gm = 4;
     p.ksplit = ksplit; p.ks_a = p.K; p.ks_b = p.K; p.ks_c = Mpad * N;
-#ifdef SF_ABLATE
-    p.cyc = 0; p.stagger = 0;
-#endif
     SF_CHECK_ARG(256L * lda * 2 < (1L << 31) && 256L * ldb * 2 < (1L << 31), "sf_gemm_nt: row stride too large for the 256-tile kernel");
     const long units = tiles * ksplit;
     const int sched = N <= 8192 ? 12 : 13;

@@ -28,9 +28,8 @@
 //     only after (own reads returned: lgkmcnt(0)) + barrier; its k-half-0 fragments were read in iteration t-1.
 //   * round-1 schedule (one barrier per K-tile, groups of 4 MFMAs + 2 reads, DMA in the second half-step, vmcnt(0)):
 //     30 % more cycles than hipBLASLt on the same shape; this one 10 % (SQ_WAVE_CYCLES, profiles/old/r2_gemm_pmc.txt).
-//     Cycles per K-tile read inside the kernel (tools build, SF_GEMM_CYC): MFMAs alone 2083, this loop 2251
-//     (profiles/old/r2_gemm_cycles.jsonl).
-//     It and the intermediate plans live in tools/experiments/sf_gemm256w4_sched.inc (tools build only).
+//     Cycles per K-tile read inside the kernel: MFMAs alone 2083, this loop 2251 (profiles/old/r2_gemm_cycles.jsonl).
+//     It and the intermediate plans are in the history of this file.
 #pragma once
 #include "sf_api_internal.h"
 #include "sf_util.h"
@@ -76,12 +75,8 @@ struct GemmW4Args {
     // accumulation order does not depend on the tile it is in).  Set by the launcher for M >= 256, beta == 0, no in-place residual.
     int mshift = 0;
     // round 6: 1 = whole tiles of the bf16 residual form transpose in REGISTERS (v_permlane16_swap of packed column-block pairs: a lane ends
-    // up with 8 consecutive columns = 16 bytes of residual in, 16 bytes out) instead of taking the general store; 0 (tools build A/B) = as before
+    // up with 8 consecutive columns = 16 bytes of residual in, 16 bytes out) instead of taking the general store; 0 = as before
     int epi_direct = 0;
-#ifdef SF_ABLATE
-    int stagger;
-    int cyc;   // tools build: wave 0 of every workgroup overwrites C[m0][n0..n0+1] with its K-loop cycle count (fp32 bits)
-#endif
 };
 
 namespace {
@@ -103,7 +98,6 @@ SF_DEVICE void w4_barrier() { sfemu::block_barrier(); }
 SF_DEVICE void w4_wait_all() {}
 SF_DEVICE void w4_wait_lgkm() {}
 SF_DEVICE void w4_wait_vm16() {}
-SF_DEVICE void w4_wait_vm13() {}
 SF_DEVICE void w4_wait_vm32() {}
 SF_DEVICE void w4_wait_vm63() {}
 SF_DEVICE void w4_wait_vm0() {}
@@ -113,7 +107,6 @@ SF_DEVICE void w4_barrier() { __builtin_amdgcn_s_barrier(); }
 SF_DEVICE void w4_wait_all() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); }
 SF_DEVICE void w4_wait_lgkm() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 SF_DEVICE void w4_wait_vm16() { asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); }   // all but the newest 16 LDS-DMA pieces
-SF_DEVICE void w4_wait_vm13() { asm volatile("s_waitcnt vmcnt(13)" ::: "memory"); }
 SF_DEVICE void w4_wait_vm32() { asm volatile("s_waitcnt vmcnt(32)" ::: "memory"); }
 SF_DEVICE void w4_wait_vm63() { asm volatile("s_waitcnt vmcnt(63)" ::: "memory"); }
 SF_DEVICE void w4_wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
@@ -220,15 +213,9 @@ struct W4PlanAFirst {   // A (activations) first: faster for wide N
     }
     static constexpr int rd0(int r) { return 110 + r + (r >= 8 ? 1 : 0); }
 };
-#ifdef SF_ABLATE
-#include "../../tools/experiments/sf_gemm256w4_sched.inc"
-#else
 template <int SCHED> using W4PlanFor = std::conditional_t<SCHED == 13, W4PlanAFirst, W4PlanBFirst>;
-#endif
 
-// SCHED: 12 = W4PlanBFirst, 13 = W4PlanAFirst (product); 0 and 2..11 exist in the tools build only.
-// ABL (tools build, timing ablations of the round-1 schedule only, results are wrong): bit0 = no ds_reads after the first
-// tile, bit1 = no DMA in the loop, ...
+// SCHED: 12 = W4PlanBFirst, 13 = W4PlanAFirst.
 // ADD: 0 = plain, 1 = + fp32 row-mapped addend in the epilogue, before the single bf16 rounding (sf_gemm_nt_rowadd), 2 = d(SwiGLU) in the bf16 epilogue
 // (sf_gemm_nt_swiglu_bwd; whole tiles only -- its launcher guarantees it), 3 = SwiGLU forward in the bf16 epilogue of the fused
 // gate|up projection (sf_gemm_nt_swiglu_fwd; whole tiles only), 4 = teacher head: column tiles from red_n0 on are reduced (row max,
@@ -236,7 +223,7 @@ template <int SCHED> using W4PlanFor = std::conditional_t<SCHED == 13, W4PlanAFi
 // the gate AND the up rows of act columns tn*128 .. +127, interleaved 16 / 16 along its 256 B rows, so that a lane's accumulators
 // [i][2 jj] / [i][2 jj + 1] are gate / up of the SAME 4 columns: gate|up leave in their natural [M, 2I] layout (the backward reads
 // them), act = round(silu(gate)) * up leaves beside them, and the separate pass over gate|up (0.94 GB read per call) is gone
-template <int OUT_F32, int ADD = 0, int SCHED = 12, int ABL = 0>
+template <int OUT_F32, int ADD = 0, int SCHED = 12>
 SF_GLOBAL void SF_LAUNCH_BOUNDS(256, 1) gemm_nt_256w4_kernel(GemmW4Args p) {
     SF_DYN_SMEM(smem);
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = sf_wave_id();
@@ -335,17 +322,6 @@ SF_GLOBAL void SF_LAUNCH_BOUNDS(256, 1) gemm_nt_256w4_kernel(GemmW4Args p) {
     };
     acc_init();
     sf_v8s f[2][16];  // [set][0..7 = B n-tiles, 8..15 = A m-tiles]
-#ifdef SF_ABLATE
-    float cyc_loop = 0.f;
-#ifndef SF_EMU
-    unsigned rt[4] = {(unsigned)__builtin_amdgcn_s_memrealtime(), 0u, 0u, 0u};   // 100 MHz: entry, loop begin, loop end, exit
-    if (p.stagger && blockIdx.x < 256u) {   // first-round workgroups start late by (rank in the stagger order) * stagger * 10 ns
-        const unsigned rank = p.stagger > 0 ? (blockIdx.x & 7u) : (blockIdx.x >> 3);   // > 0: by XCD; < 0: by slot within the XCD
-        const unsigned wait = rank * (unsigned)(p.stagger > 0 ? p.stagger : -p.stagger);
-        while ((unsigned)__builtin_amdgcn_s_memrealtime() - rt[0] < wait) __builtin_amdgcn_s_sleep(8);
-    }
-#endif
-#endif
 
     auto read_frag = [&](int set, int g, const char* buf, int ks) {
         if (g < 8) f[set][g] = *reinterpret_cast<const sf_v8s*>(buf + b_off + g * 2048 + swz[ks]);
@@ -376,58 +352,41 @@ SF_GLOBAL void SF_LAUNCH_BOUNDS(256, 1) gemm_nt_256w4_kernel(GemmW4Args p) {
             else sf_mfma16_acc(f[1][nt], f[1][8 + mt], acc[mt][nt]);
             w4_fence();
             constexpr int r1 = w4_rd1_at<P>(i), r0 = w4_rd0_at<P>(i), gd = w4_dma_at<P>(i);
-            // ABL (tools build, timing only, results are wrong): 1 = no fragment reads, 2 = no DMA, 4 = no barriers, 8 = no waits
-            constexpr bool kRd = !(ABL & 1), kDma = !(ABL & 2), kBar = !(ABL & 4), kWait = !(ABL & 8);
-            if constexpr (kRd && r1 >= 0) read_frag(1, r1, cur, 1);
+            if constexpr (r1 >= 0) read_frag(1, r1, cur, 1);
             if constexpr (P::bar1 == i && P::bar1 != P::bar2) {
-                if constexpr (kWait) w4_wait_lgkm();
-                if constexpr (kBar) w4_barrier();
+                w4_wait_lgkm();
+                w4_barrier();
             }
             if constexpr (w4_has_split<P>::value) {
                 if constexpr (w4_has_split<P>::barB(i) || w4_has_split<P>::barA(i)) {
-                    if constexpr (kWait) w4_wait_lgkm();
-                    if constexpr (kBar) w4_barrier();
+                    w4_wait_lgkm();
+                    w4_barrier();
                 }
             }
 #ifdef SF_EMU
-            if constexpr (kDma && decltype(DO_DMA)::value && gd >= 0) dma(gd, t + 2);
+            if constexpr (decltype(DO_DMA)::value && gd >= 0) dma(gd, t + 2);
 #else
-            if constexpr (kDma && decltype(DO_DMA)::value && gd >= 0)
+            if constexpr (decltype(DO_DMA)::value && gd >= 0)
                 sf_buf_glds16_m0(gd < 8 ? rawA : rawB, voff[gd], (unsigned)(t + 2) * (TK * 2));
             constexpr int gm0 = w4_m0_at<P>(i);
-            if constexpr (kDma && decltype(DO_DMA)::value && gm0 >= 0) sf_m0_set(dma_dst(gm0, t + 2));
+            if constexpr (decltype(DO_DMA)::value && gm0 >= 0) sf_m0_set(dma_dst(gm0, t + 2));
 #endif
             if constexpr (P::bar2 == i) {
-                if constexpr (kWait) {
-                    if constexpr (P::bar1 == P::bar2) w4_wait_all();
-                    else if constexpr (decltype(DO_DMA)::value && P::vm == 16) w4_wait_vm16();
-                    else w4_wait_vm0();
-                }
-                if constexpr (kBar) w4_barrier();
+                if constexpr (P::bar1 == P::bar2) w4_wait_all();
+                else if constexpr (decltype(DO_DMA)::value && P::vm == 16) w4_wait_vm16();
+                else w4_wait_vm0();
+                w4_barrier();
             }
-            if constexpr (kRd && decltype(READ_NEXT)::value && r0 >= 0) read_frag(0, r0, nxt, 0);
+            if constexpr (decltype(READ_NEXT)::value && r0 >= 0) read_frag(0, r0, nxt, 0);
             w4_fence();
         });
     };
 
     for (;;) {   // ---- tiles of this workgroup
-#ifdef SF_ABLATE
-    if constexpr (SCHED == 0) {
-#include "../../tools/experiments/sf_gemm256w4_sched0.inc"
-    } else
-#endif
     {
         using P = W4PlanFor<SCHED>;
         int t = 0;
-#if defined(SF_ABLATE) && !defined(SF_EMU)
-        const unsigned long long cyc0 = __builtin_readcyclecounter();
-        rt[1] = (unsigned)__builtin_amdgcn_s_memrealtime();
-#endif
         for (; t + 2 < nkt; ++t) tilep(P{}, std::true_type{}, std::true_type{}, t);
-#if defined(SF_ABLATE) && !defined(SF_EMU)
-        cyc_loop = (float)(__builtin_readcyclecounter() - cyc0);
-        rt[2] = (unsigned)__builtin_amdgcn_s_memrealtime();
-#endif
         if (t + 1 < nkt) { tilep(P{}, std::true_type{}, std::false_type{}, t); ++t; }
         tilep(P{}, std::false_type{}, std::false_type{}, t);
         sf_mfma_drain();   // asm MFMAs are invisible to the hazard recogniser: let the last ones retire before acc is read
@@ -556,10 +515,6 @@ SF_GLOBAL void SF_LAUNCH_BOUNDS(256, 1) gemm_nt_256w4_kernel(GemmW4Args p) {
     }
     if (reduced) {
     } else
-#ifdef SF_ABLATE
-    if ((p.cyc & 4) || ((p.cyc & 8) && (blockIdx.x & 1))) {   // timing experiments: no stores at all / only every other workgroup stores
-    } else
-#endif
     if (fast) {
         const float alpha = p.e.alpha;
         if constexpr (OUT_F32) {
@@ -763,30 +718,14 @@ SF_GLOBAL void SF_LAUNCH_BOUNDS(256, 1) gemm_nt_256w4_kernel(GemmW4Args p) {
 #pragma unroll
     for (int g = 0; g < 16; ++g) read_frag(0, g, smem, 0);
     }   // tiles
-#ifdef SF_ABLATE
-    if ((p.cyc & 3) == 1 && tid == 0) *reinterpret_cast<float*>((char*)p.e.C + ((long)m0 * p.e.ldc + n0) * (OUT_F32 ? 4 : 2)) = cyc_loop;
-#ifndef SF_EMU
-    if ((p.cyc & 3) == 2 && tid == 0) {   // timeline of this workgroup + where it ran: 6 words at the tile origin
-        rt[3] = (unsigned)__builtin_amdgcn_s_memrealtime();   // stores issued, not yet complete
-        unsigned* o = reinterpret_cast<unsigned*>((char*)p.e.C + ((long)m0 * p.e.ldc + n0) * (OUT_F32 ? 4 : 2));
-        o[0] = rt[0]; o[1] = rt[1]; o[2] = rt[2]; o[3] = rt[3];
-        o[4] = __builtin_amdgcn_s_getreg((31 << 11) | 4);   // HW_ID
-        o[5] = __builtin_amdgcn_s_getreg((31 << 11) | 20);  // XCC_ID
-    }
-#endif
-#endif
 }
-
-#ifdef SF_ABLATE
-#include "../../tools/experiments/sf_gemm256w4_variants.inc"
-#endif
 
 }  // namespace
 
 // Grid of the persistent kernel: one workgroup per CU once there are more tiles than CUs (256 on MI355X; a multiple of 8,
-// so tile t and tile t + grid sit on the same XCD).  SF_GEMM_PERSIST=0 (tools build) gives one workgroup per tile.
+// so tile t and tile t + grid sit on the same XCD).
 static inline unsigned sf_w4_grid(long nblk, int add = 0) {
-    static const int persist = sf_knob("SF_GEMM_PERSIST", 1);
+    static const int persist = 1;   // (0 = one workgroup per tile; a product constant)
     static const int cus = [] {
         int dev = 0, n = 0;
 #ifndef SF_EMU

@@ -33,28 +33,26 @@ def test_hip_library_exports_every_declared_symbol():
 
 def test_product_library_reads_no_environment_knobs():
     """ablation / variant code paths selected by SF_* environment variables must not exist in the product
-    binary -- an inherited variable could silently change (or corrupt) training.  Knobs are compile-time constants
-    unless the TOOLS build defines SF_ABLATE (specforge_amd/csrc/sf_api_internal.h)."""
+    binary -- an inherited variable could silently change (or corrupt) training.  The kernel sources build the product
+    library (and its interpreter flavour) and nothing else: no environment lookup, no tools build, no knob macro, and no
+    source pulled in from outside specforge_amd/csrc and include/."""
+    import re
+
     from specforge_amd import build
 
     blob = open(build.build_hip(), "rb").read()
     for needle in (b"SF_GEMM_", b"SF_ATTN_", b"getenv"):
         assert needle not in blob, needle
     src = os.path.join(ROOT, "specforge_amd", "csrc")
+    inside = (src + os.sep, os.path.join(ROOT, "include") + os.sep)
     for f in os.listdir(src):
-        depth, guard = 0, None          # preprocessor nesting; `guard` = depth at which an SF_ABLATE block opened
         for line in open(os.path.join(src, f)):
-            t = line.strip()
-            if t.startswith(("#if", "#ifdef", "#ifndef")):
-                depth += 1
-                if guard is None and t.startswith("#ifdef SF_ABLATE"):
-                    guard = depth
-            elif t.startswith("#endif"):
-                if guard == depth:
-                    guard = None
-                depth -= 1
-            elif guard is None:
-                assert "getenv(" not in line, f"{f}: getenv outside an SF_ABLATE block: {t}"
+            for needle in ("getenv(", "SF_ABLATE", "sf_knob"):
+                assert needle not in line, f"{f}: {needle}: {line.strip()}"
+            m = re.match(r'\s*#\s*include\s*"([^"]+)"', line)
+            if m and m.group(1) != "sf_emu.h":      # (the interpreter build's own header, found through its -I tests/emu)
+                path = os.path.normpath(os.path.join(src, m.group(1)))
+                assert path.startswith(inside) and os.path.exists(path), f"{f}: includes {m.group(1)}"
 
 
 def test_product_path_has_no_cpu_fallback(monkeypatch, tmp_path):

@@ -1,13 +1,14 @@
-"""Within-process A/B of the TTT attention kernels (tools build, tools/experiments/libsfhip_ablate.so) at the headline
-shape (B 8, S 2048, nh 32, nkv 8, hd 128), interleaved rounds, random bf16 operands; prints one JSON line per
-(variant, kernel, ndiag) with the median time.
+"""Timing of the TTT attention kernels at the headline shape (B 8, S 2048, nh 32, nkv 8, hd 128), random bf16 operands;
+prints one JSON line per (library, kernel, ndiag) with the median time over interleaved rounds.
 
-    python tools/attn_bench.py [VAR=VAL[,VAR=VAL] ...]          (GPU box)   "base" = no knobs
+    python tools/attn_bench.py [--lib=PATH ...] [--shape=B,S,nh,nkv,hd]          (GPU box)
+
+Without --lib the product library is timed.  With several --lib=PATH (builds of the product library: another commit, other
+compiler flags, another SF_ATTN_KAHEAD) the libraries alternate inside every round, so that box drift cancels.
 
 MFMA work per launch: fwd 4, dQ 6, dK/dV 8 (x B*nh*hd*S^2/2); `frac` = achieved / 2.5 PFLOP/s."""
 import json
 import math
-import os
 import statistics
 import sys
 
@@ -16,12 +17,8 @@ import torch
 sys.path.insert(0, ".")
 from specforge_amd import _lib, ops  # noqa: E402
 
-_LIB = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--lib=")), os.path.join("tools", "experiments", "libsfhip_ablate.so"))
-_lib._inject_library_for_tests(_LIB)       # (--lib=...: another build of the tools library, e.g. other compiler flags)
-_lib._emulated = False
+LIBS = [a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--lib=")] or [_lib.LIB_PATH]
 dev = "cuda"
-args = [a for a in sys.argv[1:] if not a.startswith("--")]
-variants = args or ["base"]
 ROUNDS = 5
 shape = dict(B=8, S=2048, nh=32, nkv=8, hd=128)
 for a in sys.argv[1:]:
@@ -31,14 +28,9 @@ for a in sys.argv[1:]:
 NDIAG = [0, 6]
 
 
-def setenv(v):
-    for k in list(os.environ):
-        if k.startswith("SF_ATTN_"):
-            del os.environ[k]
-    if v != "base":
-        for kv in v.split(","):
-            k, val = kv.split("=")
-            os.environ[k] = val
+def use(path):
+    _lib._inject_library_for_tests(path)
+    _lib._emulated = False
 
 
 def timed(fn, iters=3):
@@ -83,25 +75,20 @@ def main():
 
     res = {}
     for rnd in range(ROUNDS + 1):           # round 0 = warm-up
-        for v in variants:
-            setenv(v)
+        for v in LIBS:
+            use(v)
             for nd in NDIAG:
                 for name, (fn, units) in kernels(nd).items():
                     if nd and name == "dkv":
                         continue             # the diagonal branches only touch fwd, pre and (through dq_init) dq
-                    try:
-                        ms = timed(fn)
-                    except Exception as ex:  # a variant that does not exist in this build
-                        ms = float("nan")
-                        if rnd == 0:
-                            print(json.dumps(dict(variant=v, kernel=name, error=str(ex)[:200])), flush=True)
+                    ms = timed(fn)
                     if rnd:
                         res.setdefault((v, name, nd), []).append(ms)
     for (v, name, nd), xs in res.items():
         ms = statistics.median(xs)
         units = dict(fwd=4.0, dq=6.0, dkv=8.0, pre=0.0)[name]
         tf = units * unit / ms / 1e9 if units else None
-        print(json.dumps(dict(variant=v, kernel=name, ndiag=nd, ms=round(ms, 4), min_ms=round(min(xs), 4),
+        print(json.dumps(dict(lib=v, kernel=name, ndiag=nd, ms=round(ms, 4), min_ms=round(min(xs), 4),
                               tflops=None if tf is None else round(tf, 1), frac=None if tf is None else round(tf / 2500.0, 3),
                               **shape)), flush=True)
 

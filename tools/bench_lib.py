@@ -1,4 +1,4 @@
-"""bench.py on another PRODUCT build of the library (e.g. one built from an earlier commit: tools/experiments/libsfhip_old.so), so that two
+"""bench.py on another PRODUCT build of the library (e.g. one built from an earlier commit), so that two
 commits can be compared inside the real step on one box.   python tools/bench_lib.py <path.so> --steps 10 --warmup 3 ...   (GPU box)"""
 import os
 import sys
