@@ -12,6 +12,9 @@ One process per GPU:
         --draft-config configs/llama3-8B-eagle3.json --features /data/hidden_states --target-head lm_head.pt \\
         --vocab-mapping vocab_mapping.pt --embedding embed_tokens.pt --batch-size 8 --max-len 2048 --epochs 1
 
+`--topk 1,2,4,8` also reports, at every log point, the share of scored rows whose target token is among the draft's k best logits per TTT
+step and the optimistic tree bound built from those rates (specforge_amd.eagle3.TopKAccumulator), over the steps since the last report.
+
 `--synthetic N` writes N random samples of the right shapes instead of reading --features (smoke runs, no data needed).
 """
 import argparse
@@ -27,7 +30,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))) 
 import torch
 import torch.distributed as dist
 
-from specforge_amd.eagle3 import Eagle3TrainStrategy, OnlineEagle3Model, TargetHead
+from specforge_amd.eagle3 import Eagle3TrainStrategy, OnlineEagle3Model, TargetHead, TopKAccumulator
 from specforge_amd.ingest import HiddenStateIngest
 from specforge_amd.model import DraftConfig, LlamaForCausalLMEagle3
 from specforge_amd.training import BF16Optimizer, HipDPTrainingBackend, TrainerCore
@@ -49,9 +52,11 @@ def main():
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--max-grad-norm", type=float, default=0.5)
     ap.add_argument("--lk-loss-type", choices=["alpha", "lambda"], default=None)
+    ap.add_argument("--topk", default="", help="comma-separated k (at most 8, ascending), e.g. 1,2,4,8: report top-k hit rates per TTT step")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--output", default="eagle3_draft.pt")
     args = ap.parse_args()
+    topk = tuple(int(k) for k in args.topk.split(",") if k.strip())
 
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", "1"), ("RANK", "0"), ("LOCAL_RANK", "0")))
     torch.cuda.set_device(local)
@@ -95,7 +100,7 @@ def main():
     ingest = HiddenStateIngest(files, batch_size=args.batch_size, max_len=args.max_len, target_hidden_size=cfg.target_hidden_size,
                                device=dev, dp_rank=rank, dp_size=world, seed=args.seed)
     steps_total = max(1, ingest.batches_per_epoch() * args.epochs // args.accumulation_steps)
-    eagle = OnlineEagle3Model(model, length=args.ttt_length, lk_loss_type=args.lk_loss_type).train()
+    eagle = OnlineEagle3Model(model, length=args.ttt_length, lk_loss_type=args.lk_loss_type, topk=topk).train()
     strategy = Eagle3TrainStrategy(eagle, target_head=head)
     backend = HipDPTrainingBackend(optimizer_factory=lambda m: BF16Optimizer(m, lr=args.lr, max_grad_norm=args.max_grad_norm,
                                                                              total_steps=steps_total))
@@ -103,16 +108,25 @@ def main():
     core = TrainerCore(strategy, backend, accumulation_steps=args.accumulation_steps)
 
     t0, tokens = time.perf_counter(), 0
+    hits = TopKAccumulator(topk) if topk else None
     for epoch in range(args.epochs):
         for batch in ingest.epoch(epoch):
             res = core.train_step(batch)
             tokens += batch.tensors["input_ids"].numel() * world
+            if hits is not None and rank == 0:
+                hits.update(res.metrics)
             if res.stepped and rank == 0 and core.global_step % 10 == 0:
                 torch.cuda.synchronize()
                 acc = float(torch.stack(res.metrics["acces"]).mean())
                 print(f"step {core.global_step}/{steps_total} loss {float(res.loss):.4f} acc {acc:.3f} "
                       f"grad_norm {float(res.grad_norm):.3f} lr {backend.optimizer.get_learning_rate():.2e} "
                       f"{tokens / (time.perf_counter() - t0):.0f} tok/s", flush=True)
+                if hits is not None:        # (this rank's batches since the last report)
+                    sm = hits.summary()
+                    for k in topk:
+                        rates = " ".join(f"{sm[f'top{k}_acc_{i}']:.3f}" for i in range(args.ttt_length))
+                        print(f"  top-{k} hit rate per step: {rates}   simulated_acc_len_top{k} {sm[f'simulated_acc_len_top{k}']:.3f}", flush=True)
+                    hits = TopKAccumulator(topk)
     if rank == 0:
         state = backend.state_dict()
         torch.save(strategy.checkpoint_state_filter(state["model"]), args.output)   # reference draft checkpoint keys

@@ -148,6 +148,23 @@ int sf_reduce_sum(const float* in, long n, int nsegments, float* out, float scal
 int sf_eagle3_metrics(const float* met, const int* loss_mask_pad, const int* pos_mask_pad, int B, int S, int Spad, int T, float* out,
                       void* stream);
 
+/* ---- rank of the target token in the draft's logits, and per-row top-k hits (additive to ABI 6) ----------------------------
+ * EAGLE3 drafts are served as top-k trees; the accuracy of the fused CE is top-1 only.  One streaming pass per row of draft logits
+ * z[V] (bf16 or fp32: the dtype / ld convention of the fused CE; ld a multiple of 8 and >= V, V of any size; the logits are only read).
+ * Addressing is the fused CE's: row r = b*S+s reads loss_mask_pad / tgt_ids_pad at padded index b*Spad+s+off; with row_map, r is a
+ * compact row and row_map[r] its token row.  tgt_ids_pad holds TARGET-vocabulary ids; t2d_index (int32 [Vt], optional) maps a target
+ * id to its draft index or -1 (the inverse of d2t, which must be injective); NULL = identity (Vt ignored).  With t the draft index:
+ *     rank = #{ j : z_j > z_t } + #{ j < t : z_j == z_t }
+ * compared as fp32 (exact for both dtypes); ties go to the lower index (torch.argmax), so rank == 0 exactly when the fused CE's
+ * row_correct counts the row.  SENTINEL: rank = V for a row whose loss mask is 0, whose target id is < 0 or >= Vt (>= V without
+ * t2d_index), or whose target has no draft index -- and such a row is a hit at NO threshold, whatever its value (kk[j] > V included).
+ * Outputs: row_rank int32 [rows] (optional); row_hit fp32 [J, rows] (J <= 8 thresholds kk[0..J), a HOST array read during the call,
+ * each >= 1): row_hit[j][r] = loss_mask * [rank < kk[j]] for a ranked row, 0 for a sentinel row -- laid out so that
+ * sf_reduce_sum(row_hit, rows, J, out, 1.0) gives the J hit counts.  No atomics: bitwise repeatable. */
+int sf_topk_rank(const void* logits, int dtype, long ld, int rows, int V, int S, int Spad, int off, const int* loss_mask_pad,
+                 const long long* tgt_ids_pad, const int* t2d_index, int Vt, const long long* row_map, int J, const int* kk,
+                 int* row_rank, float* row_hit, void* stream);
+
 /* ---- teacher soft targets from target logits ---------------------------------------------
  * replaces specforge/algorithms/eagle3/model.py:487-501 (_compute_target_p): argmax id
  * (lowest index on ties), position_mask = t2d[id]*loss_mask, target_p = softmax over the

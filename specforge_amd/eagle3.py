@@ -105,12 +105,14 @@ class OnlineEagle3Model(nn.Module):
 
     def __init__(self, draft_model: LlamaForCausalLMEagle3, length: int = 7, attention_backend: str = "hip",
                  lk_loss_type: Optional[str] = None, kl_scale: float = 1.0, kl_decay: float = 1.0,
-                 ploss_decay: float = 0.8, sp_group=None, sp_ulysses_group=None, sp_ring_group=None, mrope_analytic: bool = False):
+                 ploss_decay: float = 0.8, sp_group=None, sp_ulysses_group=None, sp_ring_group=None, mrope_analytic: bool = False, topk=()):
         """``attention_backend="usp"``: Ulysses sequence parallelism over ``sp_group`` (set here, or later by
         ``HipDPTrainingBackend.prepare_model`` / the strategy, before the first forward); every other value runs the one-rank
         attention.  ``sp_ring_group`` (with ``sp_ulysses_group``, None for a pure ring): ring x Ulysses over the same SP group
         (training.make_usp_groups); ``sp_group`` alone is pure Ulysses.  ``mrope_analytic``: ``Eagle3Engine.mrope_analytic`` (rope_type
-        'mrope': angles computed on the device from the ids -- no table limits; off by default)."""
+        'mrope': angles computed on the device from the ids -- no table limits; off by default).  ``topk``: ``Eagle3Engine.topk`` -- up to 8
+        ascending ints k; after every forward ``last_topk`` holds, per TTT step, the [len(topk)] counts of rows whose target token is in
+        the draft's top k (denominators: ``acc_denoms``).  The return tuple of ``forward`` is the reference's seven lists either way."""
         super().__init__()
         if lk_loss_type not in (None, "alpha", "lambda"):
             raise ValueError(f"Unknown lk loss type: {lk_loss_type}")  # core/lk_loss.py:99
@@ -124,6 +126,8 @@ class OnlineEagle3Model(nn.Module):
         self.lk_loss_type, self.kl_scale, self.kl_decay = lk_loss_type, kl_scale, kl_decay
         self.ploss_decay = ploss_decay
         self.mrope_analytic = mrope_analytic
+        self.topk = Eagle3Engine._check_topk(topk)
+        self.last_topk = None
         self._engine: Optional[Eagle3Engine] = None
         dev = next(draft_model.parameters()).device
         self._anchor = nn.Parameter(torch.zeros((), device=dev), requires_grad=True)
@@ -143,7 +147,7 @@ class OnlineEagle3Model(nn.Module):
             self._engine = Eagle3Engine(self.draft_model, ttt_length=self.length, ploss_decay=self.ploss_decay,
                                         lk_loss_type=self.lk_loss_type, kl_scale=self.kl_scale, kl_decay=self.kl_decay,
                                         sp_group=sp_group, sp_ulysses_group=uly_group, sp_ring_group=ring_group,
-                                        mrope_analytic=self.mrope_analytic)
+                                        mrope_analytic=self.mrope_analytic, topk=self.topk)
             object.__setattr__(self.draft_model, "_hip_engine", self._engine)   # found by BF16Optimizer(draft_model)
         return self._engine
 
@@ -170,6 +174,8 @@ class OnlineEagle3Model(nn.Module):
             raise NotImplementedError("past_key_values is unused by EAGLE3 training (eagle3/model.py:262)")
         train = torch.is_grad_enabled() and self.training
         dev = self.engine.dev
+        if self.engine.topk != tuple(self.topk):
+            self.engine.topk = self.topk
         if position_span is None and position_ids is not None and not position_ids.is_cuda and position_ids.numel():
             position_span = (int(position_ids.min()), int(position_ids.max()))
         to = lambda t: None if t is None else t.to(dev)
@@ -182,6 +188,7 @@ class OnlineEagle3Model(nn.Module):
         if train:
             plosses = _TTTStep.apply(self._anchor, self.engine, plosses)
         self.last_artifacts = dict(target_token_ids=out["target_token_ids"], position_mask=out["position_mask"])
+        self.last_topk = out.get("topk_corrects")
         return (list(plosses.unbind(0)), out["acceptance_rates"], out["acces"], out["acc_corrects"], out["acc_denoms"],
                 out["metric_losses"], out["metric_loss_denoms"])
 
@@ -315,14 +322,65 @@ class Eagle3TrainStrategy:
         weights = [self.ploss_decay ** i for i in range(len(plosses))]
         loss = sum(weights[i] * plosses[i] for i in range(len(plosses)))
         d = lambda xs: [x.detach() for x in xs]
-        return StepOutput(loss=loss, metrics=dict(plosses=d(plosses), acces=d(acces), acceptance_rates=d(acceptance_rates),
-                                                  acc_corrects=d(acc_corrects), acc_denoms=d(acc_denoms),
-                                                  metric_losses=d(metric_losses), metric_loss_denoms=d(metric_loss_denoms)))
+        metrics = dict(plosses=d(plosses), acces=d(acces), acceptance_rates=d(acceptance_rates), acc_corrects=d(acc_corrects),
+                       acc_denoms=d(acc_denoms), metric_losses=d(metric_losses), metric_loss_denoms=d(metric_loss_denoms))
+        tk = self.eagle3_model.last_topk
+        if tk is not None:      # top{k}_corrects: T 0-dim counts each, the shape of acc_corrects (the reference's trainer and evaluator skip them)
+            for j, kth in enumerate(self.eagle3_model.topk):
+                metrics[f"top{kth}_corrects"] = [step[j].detach() for step in tk]
+        return StepOutput(loss=loss, metrics=metrics)
 
     def checkpoint_state_filter(self, state_dict: Dict[str, Any]) -> Dict[str, Any]:
         """strip ``draft_model.``, drop the frozen embedding and engine internals (strategies/base.py:306-319)"""
         return {k.replace("draft_model.", ""): v for k, v in state_dict.items()
                 if "draft_model." in k and "embed" not in k.lower()}
+
+
+class TopKAccumulator:
+    """Top-k hit rates of a draft over many batches: float64 sums of ``top{k}_corrects`` and ``acc_denoms`` per TTT step, the ratio taken
+    after the sums (the reference's Evaluator forms its per-position accuracy the same way, eval/evaluator.py:47-93, 142-150).
+
+    ``summary()`` -> ``top{k}_acc_{i}`` (the share of step i's scored rows whose target token is among the draft's k best) and
+    ``simulated_acc_len_top{k}`` = a0 + a0*a1 + ... over those rates: the Evaluator's ``_simulated_acc_len`` recurrence.  For k = 1 it is
+    the reference's expected accepted length of a chain draft.  For k > 1 it is an OPTIMISTIC bound for a top-k tree: it assumes the tree
+    keeps every one of the k candidates at every depth (k^depth nodes) and that the per-depth rates, measured along the teacher-forced
+    path, carry over to whichever branch was accepted; a served tree prunes to a node budget and accepts less."""
+
+    def __init__(self, topk):
+        self.topk = Eagle3Engine._check_topk(topk)
+        self.corrects: Optional[torch.Tensor] = None        # [len(topk), T] float64
+        self.denoms: Optional[torch.Tensor] = None          # [T] float64
+
+    def update(self, metrics: Dict[str, Any]) -> None:
+        """``metrics`` = ``StepOutput.metrics`` of a strategy whose model has ``topk`` set"""
+        # (sums stay on the metrics' device: no read-back per batch, ``summary`` pays one)
+        c = torch.stack([torch.stack([torch.as_tensor(v).detach().double() for v in metrics[f"top{k}_corrects"]]) for k in self.topk])
+        den = torch.stack([torch.as_tensor(v).detach().double() for v in metrics["acc_denoms"]]).to(c.device)
+        # (acc_denoms is the count of scored rows clamped to >= 1e-6: a step without any contributes no rows)
+        den = torch.where(den >= 1.0, den, torch.zeros_like(den))
+        if self.corrects is None:
+            self.corrects, self.denoms = torch.zeros_like(c), torch.zeros_like(den)
+        self.corrects += c
+        self.denoms += den
+
+    @staticmethod
+    def simulated_acc_len(rates) -> float:
+        cumulative, total = 1.0, 0.0
+        for a in rates:
+            cumulative *= float(a)
+            total += cumulative
+        return total
+
+    def summary(self) -> Dict[str, float]:
+        if self.corrects is None:
+            return {}
+        out: Dict[str, float] = {}
+        for j, k in enumerate(self.topk):
+            rates = (self.corrects[j] / self.denoms.clamp_min(1.0)).cpu().tolist()
+            for i, a in enumerate(rates):
+                out[f"top{k}_acc_{i}"] = float(a)
+            out[f"simulated_acc_len_top{k}"] = self.simulated_acc_len(rates)
+        return out
 
 
 @dataclass

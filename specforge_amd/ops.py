@@ -202,6 +202,29 @@ def eagle3_metrics(met: torch.Tensor, loss_mask_pad: torch.Tensor, pos_mask_pad:
     _lib.check(L.sf_eagle3_metrics(_p(met), _p(loss_mask_pad), _p(pos_mask_pad), B, S, Spad, T, _p(out), _stream()), "sf_eagle3_metrics")
 
 
+TOPK_MAX = 8      # thresholds per sf_topk_rank launch
+
+
+def topk_rank(logits: torch.Tensor, *, S: int, Spad: int, off: int, loss_mask_pad, tgt_ids_pad, t2d_index=None, kk: Sequence[int] = (),
+              row_rank=None, row_hit=None, row_map=None):
+    """Rank of each row's target token in its draft logits (ties to the lower index; V = no rank: loss mask 0 or a target outside the
+    draft vocabulary) and ``row_hit`` [len(kk), rows] fp32 = loss_mask * (rank < kk[j]); see include/specforge_amd.h.  ``t2d_index``
+    int32 [Vt]: target id -> draft index or -1 (None: identity); addressing (S, Spad, off, row_map) as ``ce_fused``.  Reads only."""
+    L = _lib.lib()
+    rows, V = logits.shape
+    kk = [int(k) for k in kk]
+    J = len(kk)
+    assert loss_mask_pad.dtype == torch.int32 and tgt_ids_pad.dtype == torch.int64 and loss_mask_pad.is_contiguous() and tgt_ids_pad.is_contiguous()
+    assert t2d_index is None or (t2d_index.dtype == torch.int32 and t2d_index.is_contiguous())
+    assert row_map is None or (row_map.dtype == torch.int64 and row_map.numel() >= rows and row_map.is_contiguous())
+    assert row_rank is None or (row_rank.dtype == torch.int32 and row_rank.numel() >= rows and row_rank.is_contiguous())
+    assert J == 0 or (row_hit is not None and row_hit.dtype == torch.float32 and row_hit.numel() >= J * rows and row_hit.is_contiguous())
+    arr = (ctypes.c_int * max(1, J))(*kk)
+    _lib.check(L.sf_topk_rank(_p(logits), _dt(logits), _rowmajor(logits), rows, V, S, Spad, off, _p(loss_mask_pad), _p(tgt_ids_pad),
+                              _p(t2d_index), t2d_index.numel() if t2d_index is not None else 0, _p(row_map), J, arr, _p(row_rank),
+                              _p(row_hit) if J else None, _stream()), "sf_topk_rank")
+
+
 def teacher_reduce(z: torch.Tensor, *, Vd: int, d2t, t2d_u8, loss_mask_pad, S: int, Spad: int, target_p_pad,
                    pod_scale_pad, tsum_pad, ids_pad, pos_mask_pad, row0: int = 0):
     """rows of z are tokens row0 .. row0+rows (row index b*S+s)."""
