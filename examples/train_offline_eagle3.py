@@ -14,6 +14,8 @@ One process per GPU:
 
 `--topk 1,2,4,8` also reports, at every log point, the share of scored rows whose target token is among the draft's k best logits per TTT
 step and the optimistic tree bound built from those rates (specforge_amd.eagle3.TopKAccumulator), over the steps since the last report.
+`--chain` reports beside it the share of chains still accepted at each depth, from the joint hits of every row over the TTT steps, and
+their sum, the teacher-forced accepted length (specforge_amd.eagle3.ChainAccumulator): for top-1, and for every k of `--topk`.
 
 `--synthetic N` writes N random samples of the right shapes instead of reading --features (smoke runs, no data needed).
 """
@@ -30,7 +32,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))) 
 import torch
 import torch.distributed as dist
 
-from specforge_amd.eagle3 import Eagle3TrainStrategy, OnlineEagle3Model, TargetHead, TopKAccumulator
+from specforge_amd.eagle3 import ChainAccumulator, Eagle3TrainStrategy, OnlineEagle3Model, TargetHead, TopKAccumulator
 from specforge_amd.ingest import HiddenStateIngest
 from specforge_amd.model import DraftConfig, LlamaForCausalLMEagle3
 from specforge_amd.training import BF16Optimizer, HipDPTrainingBackend, TrainerCore
@@ -53,6 +55,7 @@ def main():
     ap.add_argument("--max-grad-norm", type=float, default=0.5)
     ap.add_argument("--lk-loss-type", choices=["alpha", "lambda"], default=None)
     ap.add_argument("--topk", default="", help="comma-separated k (at most 8, ascending), e.g. 1,2,4,8: report top-k hit rates per TTT step")
+    ap.add_argument("--chain", action="store_true", help="report the accepted length of the draft chains from the joint hits (top-1 and every --topk k)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--output", default="eagle3_draft.pt")
     args = ap.parse_args()
@@ -100,7 +103,7 @@ def main():
     ingest = HiddenStateIngest(files, batch_size=args.batch_size, max_len=args.max_len, target_hidden_size=cfg.target_hidden_size,
                                device=dev, dp_rank=rank, dp_size=world, seed=args.seed)
     steps_total = max(1, ingest.batches_per_epoch() * args.epochs // args.accumulation_steps)
-    eagle = OnlineEagle3Model(model, length=args.ttt_length, lk_loss_type=args.lk_loss_type, topk=topk).train()
+    eagle = OnlineEagle3Model(model, length=args.ttt_length, lk_loss_type=args.lk_loss_type, topk=topk, chain=args.chain).train()
     strategy = Eagle3TrainStrategy(eagle, target_head=head)
     backend = HipDPTrainingBackend(optimizer_factory=lambda m: BF16Optimizer(m, lr=args.lr, max_grad_norm=args.max_grad_norm,
                                                                              total_steps=steps_total))
@@ -109,12 +112,16 @@ def main():
 
     t0, tokens = time.perf_counter(), 0
     hits = TopKAccumulator(topk) if topk else None
+    chain_ks = tuple(sorted({1, *topk}))
+    chains = ChainAccumulator(chain_ks) if args.chain else None
     for epoch in range(args.epochs):
         for batch in ingest.epoch(epoch):
             res = core.train_step(batch)
             tokens += batch.tensors["input_ids"].numel() * world
             if hits is not None and rank == 0:
                 hits.update(res.metrics)
+            if chains is not None and rank == 0:
+                chains.update(res.metrics)
             if res.stepped and rank == 0 and core.global_step % 10 == 0:
                 torch.cuda.synchronize()
                 acc = float(torch.stack(res.metrics["acces"]).mean())
@@ -127,6 +134,12 @@ def main():
                         rates = " ".join(f"{sm[f'top{k}_acc_{i}']:.3f}" for i in range(args.ttt_length))
                         print(f"  top-{k} hit rate per step: {rates}   simulated_acc_len_top{k} {sm[f'simulated_acc_len_top{k}']:.3f}", flush=True)
                     hits = TopKAccumulator(topk)
+                if chains is not None:
+                    sm = chains.summary()
+                    for k in chain_ks:
+                        rates = " ".join(f"{sm[f'chain_top{k}_acc_{i}']:.3f}" for i in range(args.ttt_length))
+                        print(f"  top-{k} chains alive per depth: {rates}   chain_acc_len_top{k} {sm[f'chain_acc_len_top{k}']:.3f}", flush=True)
+                    chains = ChainAccumulator(chain_ks)
     if rank == 0:
         state = backend.state_dict()
         torch.save(strategy.checkpoint_state_filter(state["model"]), args.output)   # reference draft checkpoint keys

@@ -165,6 +165,22 @@ int sf_topk_rank(const void* logits, int dtype, long ld, int rows, int V, int S,
                  const long long* tgt_ids_pad, const int* t2d_index, int Vt, const long long* row_map, int J, const int* kk,
                  int* row_rank, float* row_hit, void* stream);
 
+/* ---- joint accepted length of the draft chains over the TTT steps (additive to ABI 6) ---------------------------------------
+ * Row s of the [B, S] grid is one draft chain through every TTT step; one call per step, in ascending off, folds that step's per-row
+ * hits into per-token-row state.  The caller zeroes chain_depth int32 [ntok] and chain_len int32 [1+J, ntok] before off = 0 (so
+ * off = 0 is no special case).  Row r is token row rt = row_map ? row_map[r] : r = b*S+s and reads loss_mask_pad at b*Spad+s+off (the
+ * addressing of sf_topk_rank); ntok = B*S.  Channel 0's hit is row_correct[r] != 0 (the fused CE's), channel 1+j's is
+ * row_hit[j][r] != 0 (row_hit fp32 [J, rows] of sf_topk_rank; NULL with J = 0; J <= 8).
+ *     eligible = loss_mask != 0 && chain_depth[rt] == off        -> chain_depth[rt] = off + 1
+ *     alive_h  = eligible && chain_len[h][rt] == off && hit_h    -> chain_len[h][rt] = off + 1
+ * A step without a loss mask censors the chain for good (it is no miss), a miss ends it, neither revives -- also for a row that a
+ * step's row_map leaves out.  row_out fp32 [2+J, rows]: row_out[0][r] = eligible, row_out[1+h][r] = alive_h as 0.f / 1.f, laid out
+ * so that sf_reduce_sum(row_out, rows, 2+J, out, 1.0) gives the step's counts.  row_map entries must be DISTINCT (two rows of one
+ * token row would race on its state); an entry outside [0, ntok) writes zeros to its outputs and touches no state.  Plain loads and
+ * stores, no atomics: bitwise repeatable.  rows == 0 launches nothing. */
+int sf_chain_step(int rows, int S, int Spad, int off, long ntok, const int* loss_mask_pad, const long long* row_map,
+                  const float* row_correct, const float* row_hit, int J, int* chain_depth, int* chain_len, float* row_out, void* stream);
+
 /* ---- teacher soft targets from target logits ---------------------------------------------
  * replaces specforge/algorithms/eagle3/model.py:487-501 (_compute_target_p): argmax id
  * (lowest index on ties), position_mask = t2d[id]*loss_mask, target_p = softmax over the

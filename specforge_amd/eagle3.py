@@ -105,14 +105,18 @@ class OnlineEagle3Model(nn.Module):
 
     def __init__(self, draft_model: LlamaForCausalLMEagle3, length: int = 7, attention_backend: str = "hip",
                  lk_loss_type: Optional[str] = None, kl_scale: float = 1.0, kl_decay: float = 1.0,
-                 ploss_decay: float = 0.8, sp_group=None, sp_ulysses_group=None, sp_ring_group=None, mrope_analytic: bool = False, topk=()):
+                 ploss_decay: float = 0.8, sp_group=None, sp_ulysses_group=None, sp_ring_group=None, mrope_analytic: bool = False, topk=(),
+                 chain: bool = False):
         """``attention_backend="usp"``: Ulysses sequence parallelism over ``sp_group`` (set here, or later by
         ``HipDPTrainingBackend.prepare_model`` / the strategy, before the first forward); every other value runs the one-rank
         attention.  ``sp_ring_group`` (with ``sp_ulysses_group``, None for a pure ring): ring x Ulysses over the same SP group
         (training.make_usp_groups); ``sp_group`` alone is pure Ulysses.  ``mrope_analytic``: ``Eagle3Engine.mrope_analytic`` (rope_type
         'mrope': angles computed on the device from the ids -- no table limits; off by default).  ``topk``: ``Eagle3Engine.topk`` -- up to 8
         ascending ints k; after every forward ``last_topk`` holds, per TTT step, the [len(topk)] counts of rows whose target token is in
-        the draft's top k (denominators: ``acc_denoms``).  The return tuple of ``forward`` is the reference's seven lists either way."""
+        the draft's top k (denominators: ``acc_denoms``).  The return tuple of ``forward`` is the reference's seven lists either way.
+        ``chain``: ``Eagle3Engine.chain`` -- the joint accepted length of the draft chains; after every forward ``last_chain`` =
+        (denoms, corrects): per TTT step the count of rows with a loss mask at every depth so far, and the [1 + len(topk)] counts of
+        those that hit at every depth so far (channel 0 top-1, then ``topk``); None when off."""
         super().__init__()
         if lk_loss_type not in (None, "alpha", "lambda"):
             raise ValueError(f"Unknown lk loss type: {lk_loss_type}")  # core/lk_loss.py:99
@@ -128,6 +132,8 @@ class OnlineEagle3Model(nn.Module):
         self.mrope_analytic = mrope_analytic
         self.topk = Eagle3Engine._check_topk(topk)
         self.last_topk = None
+        self.chain = bool(chain)
+        self.last_chain = None
         self._engine: Optional[Eagle3Engine] = None
         dev = next(draft_model.parameters()).device
         self._anchor = nn.Parameter(torch.zeros((), device=dev), requires_grad=True)
@@ -147,7 +153,7 @@ class OnlineEagle3Model(nn.Module):
             self._engine = Eagle3Engine(self.draft_model, ttt_length=self.length, ploss_decay=self.ploss_decay,
                                         lk_loss_type=self.lk_loss_type, kl_scale=self.kl_scale, kl_decay=self.kl_decay,
                                         sp_group=sp_group, sp_ulysses_group=uly_group, sp_ring_group=ring_group,
-                                        mrope_analytic=self.mrope_analytic, topk=self.topk)
+                                        mrope_analytic=self.mrope_analytic, topk=self.topk, chain=self.chain)
             object.__setattr__(self.draft_model, "_hip_engine", self._engine)   # found by BF16Optimizer(draft_model)
         return self._engine
 
@@ -176,6 +182,8 @@ class OnlineEagle3Model(nn.Module):
         dev = self.engine.dev
         if self.engine.topk != tuple(self.topk):
             self.engine.topk = self.topk
+        if self.engine.chain != bool(self.chain):
+            self.engine.chain = self.chain
         if position_span is None and position_ids is not None and not position_ids.is_cuda and position_ids.numel():
             position_span = (int(position_ids.min()), int(position_ids.max()))
         to = lambda t: None if t is None else t.to(dev)
@@ -189,6 +197,7 @@ class OnlineEagle3Model(nn.Module):
             plosses = _TTTStep.apply(self._anchor, self.engine, plosses)
         self.last_artifacts = dict(target_token_ids=out["target_token_ids"], position_mask=out["position_mask"])
         self.last_topk = out.get("topk_corrects")
+        self.last_chain = (out["chain_denoms"], out["chain_corrects"]) if "chain_denoms" in out else None
         return (list(plosses.unbind(0)), out["acceptance_rates"], out["acces"], out["acc_corrects"], out["acc_denoms"],
                 out["metric_losses"], out["metric_loss_denoms"])
 
@@ -328,6 +337,11 @@ class Eagle3TrainStrategy:
         if tk is not None:      # top{k}_corrects: T 0-dim counts each, the shape of acc_corrects (the reference's trainer and evaluator skip them)
             for j, kth in enumerate(self.eagle3_model.topk):
                 metrics[f"top{kth}_corrects"] = [step[j].detach() for step in tk]
+        ch = self.eagle3_model.last_chain
+        if ch is not None:      # chain_denoms / chain_top{k}_corrects: T 0-dim counts each (k = 1, then the model's topk; a 1 in topk is named once)
+            metrics["chain_denoms"] = [x.detach() for x in ch[0]]
+            for h, kth in enumerate((1,) + tuple(self.eagle3_model.topk)):
+                metrics.setdefault(f"chain_top{kth}_corrects", [step[h].detach() for step in ch[1]])
         return StepOutput(loss=loss, metrics=metrics)
 
     def checkpoint_state_filter(self, state_dict: Dict[str, Any]) -> Dict[str, Any]:
@@ -344,7 +358,9 @@ class TopKAccumulator:
     ``simulated_acc_len_top{k}`` = a0 + a0*a1 + ... over those rates: the Evaluator's ``_simulated_acc_len`` recurrence.  For k = 1 it is
     the reference's expected accepted length of a chain draft.  For k > 1 it is an OPTIMISTIC bound for a top-k tree: it assumes the tree
     keeps every one of the k candidates at every depth (k^depth nodes) and that the per-depth rates, measured along the teacher-forced
-    path, carry over to whichever branch was accepted; a served tree prunes to a node budget and accepts less."""
+    path, carry over to whichever branch was accepted; a served tree prunes to a node budget and accepts less.  The recurrence also
+    treats the hits at different depths as independent, which they are not (hard positions miss at every depth): the exact
+    teacher-forced figure from the joint hits is ``chain_acc_len_top{k}`` of ``ChainAccumulator`` (``OnlineEagle3Model(chain=True)``)."""
 
     def __init__(self, topk):
         self.topk = Eagle3Engine._check_topk(topk)
@@ -380,6 +396,45 @@ class TopKAccumulator:
             for i, a in enumerate(rates):
                 out[f"top{k}_acc_{i}"] = float(a)
             out[f"simulated_acc_len_top{k}"] = self.simulated_acc_len(rates)
+        return out
+
+
+class ChainAccumulator:
+    """Accepted length of the draft chains over many batches, from the JOINT hits (``OnlineEagle3Model(chain=True)``): float64 sums of
+    ``chain_top{k}_corrects`` and ``chain_denoms`` per TTT depth, the ratio taken after the sums, 0 where the denominator is 0.
+
+    ``summary()`` -> ``chain_top{k}_acc_{i}``: of the rows that could be scored at every depth 0 .. i, the share whose target was among
+    the draft's k best at every one of them -- the probability that a chain (k = 1) or a full top-k tree is accepted to depth i + 1 --
+    and ``chain_acc_len_top{k}`` = their sum over i, the expected accepted length.  Teacher-forced (the inputs are the dataset's tokens,
+    hits are against the teacher's argmax, as ``acces``): exact for a greedy chain and for a full top-k tree along the true path, an
+    upper bound for a tree pruned to a node budget.  ``ks``: the channels to report, each 1 or a member of the model's ``topk``."""
+
+    def __init__(self, ks):
+        self.ks = tuple(int(k) for k in ks)
+        if not self.ks or any(k < 1 for k in self.ks) or len(set(self.ks)) != len(self.ks):
+            raise ValueError(f"ChainAccumulator: distinct positive k, got {self.ks}")
+        self.corrects: Optional[torch.Tensor] = None        # [len(ks), T] float64
+        self.denoms: Optional[torch.Tensor] = None          # [T] float64
+
+    def update(self, metrics: Dict[str, Any]) -> None:
+        """``metrics`` = ``StepOutput.metrics`` of a strategy whose model has ``chain`` set"""
+        # (sums stay on the metrics' device: no read-back per batch, ``summary`` pays one)
+        c = torch.stack([torch.stack([torch.as_tensor(v).detach().double() for v in metrics[f"chain_top{k}_corrects"]]) for k in self.ks])
+        den = torch.stack([torch.as_tensor(v).detach().double() for v in metrics["chain_denoms"]]).to(c.device)
+        if self.corrects is None:
+            self.corrects, self.denoms = torch.zeros_like(c), torch.zeros_like(den)
+        self.corrects += c
+        self.denoms += den
+
+    def summary(self) -> Dict[str, float]:
+        if self.corrects is None:
+            return {}
+        out: Dict[str, float] = {}
+        rates = torch.where(self.denoms > 0, self.corrects / self.denoms.clamp_min(1.0), torch.zeros_like(self.corrects)).cpu().tolist()
+        for j, k in enumerate(self.ks):
+            for i, a in enumerate(rates[j]):
+                out[f"chain_top{k}_acc_{i}"] = float(a)
+            out[f"chain_acc_len_top{k}"] = float(sum(rates[j]))
         return out
 
 

@@ -225,6 +225,33 @@ def topk_rank(logits: torch.Tensor, *, S: int, Spad: int, off: int, loss_mask_pa
                               _p(row_hit) if J else None, _stream()), "sf_topk_rank")
 
 
+CHAIN_MAX_ROWS = 1 << 24      # fp32 sums of the 0/1 outputs of sf_chain_step are exact below this many rows
+
+
+def chain_step(*, rows: int, S: int, Spad: int, off: int, loss_mask_pad, row_correct, chain_depth, chain_len, row_out, row_hit=None,
+               row_map=None):
+    """One TTT step of the joint chain fold (include/specforge_amd.h, sf_chain_step): ``chain_depth`` int32 [ntok] and ``chain_len``
+    int32 [1+J, ntok] advance where the row is still eligible / alive at depth ``off``; ``row_out`` fp32 [2+J, rows] = eligible and
+    alive per channel as 0/1.  Channel 0: ``row_correct`` (the fused CE's), channels 1..J: ``row_hit`` [J, rows] (``topk_rank``).
+    Addressing (S, Spad, off, row_map) as ``topk_rank``.  The caller zeroes the state before ``off = 0`` and steps in ascending order."""
+    L = _lib.lib()
+    rows = int(rows)
+    if rows >= CHAIN_MAX_ROWS:
+        raise ValueError(f"chain_step: {rows} rows; the fp32 counts are exact below {CHAIN_MAX_ROWS}")
+    ntok = chain_depth.numel()
+    assert chain_depth.dtype == torch.int32 and chain_len.dtype == torch.int32 and chain_depth.is_contiguous() and chain_len.is_contiguous()
+    assert ntok > 0 and chain_len.numel() % ntok == 0
+    J = chain_len.numel() // ntok - 1
+    assert loss_mask_pad.dtype == torch.int32 and loss_mask_pad.is_contiguous() and S > 0 and loss_mask_pad.numel() >= ntok // S * Spad
+    assert row_map is None or (row_map.dtype == torch.int64 and row_map.numel() >= rows and row_map.is_contiguous())
+    assert row_map is not None or rows <= ntok
+    assert row_correct.dtype == torch.float32 and row_correct.numel() >= rows and row_correct.is_contiguous()
+    assert J == 0 or (row_hit is not None and row_hit.dtype == torch.float32 and row_hit.numel() >= J * rows and row_hit.is_contiguous())
+    assert row_out.dtype == torch.float32 and row_out.numel() >= (2 + J) * rows and row_out.is_contiguous()
+    _lib.check(L.sf_chain_step(rows, S, Spad, off, ntok, _p(loss_mask_pad), _p(row_map), _p(row_correct), _p(row_hit) if J else None, J,
+                               _p(chain_depth), _p(chain_len), _p(row_out), _stream()), "sf_chain_step")
+
+
 def teacher_reduce(z: torch.Tensor, *, Vd: int, d2t, t2d_u8, loss_mask_pad, S: int, Spad: int, target_p_pad,
                    pod_scale_pad, tsum_pad, ids_pad, pos_mask_pad, row0: int = 0):
     """rows of z are tokens row0 .. row0+rows (row index b*S+s)."""

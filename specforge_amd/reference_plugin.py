@@ -131,7 +131,8 @@ def _training_model_factory():
         t = config.training
         check_training_topology(t, draft_config, mode=getattr(config, "mode", None))
         model = OnlineEagle3Model(draft_model=draft_model, length=t.ttt_length, attention_backend=t.attention_backend,
-                                  lk_loss_type=t.lk_loss_type, kl_scale=t.kl_scale, kl_decay=t.kl_decay, topk=_options.get("topk", ()))
+                                  lk_loss_type=t.lk_loss_type, kl_scale=t.kl_scale, kl_decay=t.kl_decay, topk=_options.get("topk", ()),
+                                  chain=_options.get("chain", False))
         model = model.to(device=mp._device(), dtype=mp._torch_dtype(config))
         target_head = None
         if config.mode == "offline" or (config.deployment.mode == "disaggregated" and t.role == "consumer"):
@@ -386,13 +387,16 @@ class _HipBackendForTrainer(HipDPTrainingBackend):
 _options: dict = {}      # settings of the HIP path that the reference's strict run schema has no key for (install(...) sets them)
 
 
-def install(override: bool = False, topk=None) -> None:
+def install(override: bool = False, topk=None, chain=None) -> None:
     """Rebind the constructors the reference hard-codes (module docstring, b3 / f1): the trainer's backend, its feature
     loader and the configured optimizer factory's class; with ``override=True`` also the draft registry entry ``LlamaForCausalLMEagle3``.
     Idempotent; ``uninstall()`` restores everything (e.g. before ``export --to sglang`` materialises the reference's
     own class from the same draft config).  ``topk`` (e.g. ``(1, 2, 4, 8)``; None leaves the setting as it is): the models the
     algorithm's factory builds from now on report top-k hit counts (``OnlineEagle3Model(topk=...)``, ``top{k}_corrects`` in
-    ``StepOutput.metrics``); ``uninstall()`` clears it."""
+    ``StepOutput.metrics``); ``chain`` (True / False; None leaves it): they also report the joint chain counts
+    (``OnlineEagle3Model(chain=...)``, ``chain_denoms`` and ``chain_top{k}_corrects``); ``uninstall()`` clears both."""
+    if chain is not None:
+        _options["chain"] = bool(chain)
     if topk is not None:
         from .engine import Eagle3Engine
 
@@ -465,7 +469,7 @@ def main(argv=None, *, worker_prefix=None) -> int:
     (default: ``python -m specforge_amd.reference_plugin``; the test suite's harness entry passes itself).  Single-node launches
     rendezvous on 127.0.0.1 (``--local-addr``: container host names need not resolve).  ``--topk 1,2,4,8`` (before or after ``train``):
     top-k hit counts in the step metrics (``install(topk=...)``; the run YAML is a strict schema and has no key for it) -- handed on to
-    spawned workers on their command line."""
+    spawned workers on their command line.  ``--chain`` beside it: the joint chain counts (``install(chain=True)``)."""
     import argparse
     import os
     import sys
@@ -473,9 +477,14 @@ def main(argv=None, *, worker_prefix=None) -> int:
     from specforge import cli
 
     argv = list(sys.argv[1:] if argv is None else argv)
-    topk_csv = None
-    if len(argv) >= 2 and argv[0] == "--topk":      # (in front of the sub-command: where a spawned worker's prefix carries it)
-        topk_csv, argv = argv[1], argv[2:]
+    topk_csv, chain_flag = None, False
+    while argv and argv[0] in ("--topk", "--chain"):    # (in front of the sub-command: where a spawned worker's prefix carries them)
+        if argv[0] == "--chain":
+            chain_flag, argv = True, argv[1:]
+        elif len(argv) >= 2:
+            topk_csv, argv = argv[1], argv[2:]
+        else:
+            break
     if not argv or argv[0] != "train":
         return cli.main(argv)
     ap = argparse.ArgumentParser(prog="python -m specforge_amd.reference_plugin train")
@@ -484,6 +493,8 @@ def main(argv=None, *, worker_prefix=None) -> int:
     ap.add_argument("--node-rank", type=int, default=None)
     ap.add_argument("--plan", action="store_true")
     ap.add_argument("--topk", default=topk_csv, help="comma-separated k, e.g. 1,2,4,8: top-k hit counts in the step metrics")
+    ap.add_argument("--chain", action="store_true", default=chain_flag,
+                    help="joint chain counts (chain_denoms, chain_top{k}_corrects) in the step metrics")
     ap.add_argument("overrides", nargs="*")
     args = ap.parse_args(argv[1:])
     topk = tuple(int(k) for k in args.topk.split(",") if k.strip()) if args.topk else None
@@ -492,13 +503,15 @@ def main(argv=None, *, worker_prefix=None) -> int:
     from specforge.config import load_config
     from specforge.launch_plan import build_launch_plan, run_commands
 
-    install(override=True, topk=topk)
+    install(override=True, topk=topk, chain=True if args.chain else None)
     cfg = load_config(args.config, args.overrides)
     check_training_topology(cfg.training, _draft_config_dict(cfg), mode=cfg.mode)    # before any process group or engine exists
     resolved = resolve_run(cfg, registry=registry(override=True))
     me = tuple(worker_prefix) if worker_prefix else (sys.executable, "-m", "specforge_amd.reference_plugin")
     if topk:
         me = me + ("--topk", ",".join(str(k) for k in topk))
+    if args.chain:
+        me = me + ("--chain",)
     plan = build_launch_plan(resolved.config, algorithm=resolved.algorithm, config_path=args.config, overrides=args.overrides,
                              requested_role=args.role, node_rank=args.node_rank, worker_prefix=me,
                              torchrun_prefix=(sys.executable, "-m", "torch.distributed.run", "--no-python", "--local-addr", "127.0.0.1"))
