@@ -16,6 +16,9 @@ One process per GPU:
 step and the optimistic tree bound built from those rates (specforge_amd.eagle3.TopKAccumulator), over the steps since the last report.
 `--chain` reports beside it the share of chains still accepted at each depth, from the joint hits of every row over the TTT steps, and
 their sum, the teacher-forced accepted length (specforge_amd.eagle3.ChainAccumulator): for top-1, and for every k of `--topk`.
+`--conf-bins 10 --conf-thresholds 0.3,0.5,0.7` reports how well the draft's own top-1 probability tracks its hits (expected calibration
+error per TTT depth) and, per threshold, the accepted and drafted tokens of a chain that stops drafting once its confidence falls under
+it (specforge_amd.eagle3.ConfidenceAccumulator).
 
 `--synthetic N` writes N random samples of the right shapes instead of reading --features (smoke runs, no data needed).
 """
@@ -32,7 +35,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))) 
 import torch
 import torch.distributed as dist
 
-from specforge_amd.eagle3 import ChainAccumulator, Eagle3TrainStrategy, OnlineEagle3Model, TargetHead, TopKAccumulator
+from specforge_amd.eagle3 import ChainAccumulator, ConfidenceAccumulator, Eagle3TrainStrategy, OnlineEagle3Model, TargetHead, TopKAccumulator
 from specforge_amd.ingest import HiddenStateIngest
 from specforge_amd.model import DraftConfig, LlamaForCausalLMEagle3
 from specforge_amd.training import BF16Optimizer, HipDPTrainingBackend, TrainerCore
@@ -56,10 +59,13 @@ def main():
     ap.add_argument("--lk-loss-type", choices=["alpha", "lambda"], default=None)
     ap.add_argument("--topk", default="", help="comma-separated k (at most 8, ascending), e.g. 1,2,4,8: report top-k hit rates per TTT step")
     ap.add_argument("--chain", action="store_true", help="report the accepted length of the draft chains from the joint hits (top-1 and every --topk k)")
+    ap.add_argument("--conf-bins", type=int, default=0, help="reliability bins (at most 32) of the draft's top-1 probability per TTT step")
+    ap.add_argument("--conf-thresholds", default="", help="comma-separated confidence thresholds in [0, 1] (at most 8, ascending), e.g. 0.3,0.5,0.7")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--output", default="eagle3_draft.pt")
     args = ap.parse_args()
     topk = tuple(int(k) for k in args.topk.split(",") if k.strip())
+    conf_tau = tuple(float(t) for t in args.conf_thresholds.split(",") if t.strip())
 
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", "1"), ("RANK", "0"), ("LOCAL_RANK", "0")))
     torch.cuda.set_device(local)
@@ -103,7 +109,8 @@ def main():
     ingest = HiddenStateIngest(files, batch_size=args.batch_size, max_len=args.max_len, target_hidden_size=cfg.target_hidden_size,
                                device=dev, dp_rank=rank, dp_size=world, seed=args.seed)
     steps_total = max(1, ingest.batches_per_epoch() * args.epochs // args.accumulation_steps)
-    eagle = OnlineEagle3Model(model, length=args.ttt_length, lk_loss_type=args.lk_loss_type, topk=topk, chain=args.chain).train()
+    eagle = OnlineEagle3Model(model, length=args.ttt_length, lk_loss_type=args.lk_loss_type, topk=topk, chain=args.chain,
+                              conf_bins=args.conf_bins, conf_thresholds=conf_tau).train()
     strategy = Eagle3TrainStrategy(eagle, target_head=head)
     backend = HipDPTrainingBackend(optimizer_factory=lambda m: BF16Optimizer(m, lr=args.lr, max_grad_norm=args.max_grad_norm,
                                                                              total_steps=steps_total))
@@ -114,6 +121,7 @@ def main():
     hits = TopKAccumulator(topk) if topk else None
     chain_ks = tuple(sorted({1, *topk}))
     chains = ChainAccumulator(chain_ks) if args.chain else None
+    confs = ConfidenceAccumulator(args.conf_bins, conf_tau) if args.conf_bins or conf_tau else None
     for epoch in range(args.epochs):
         for batch in ingest.epoch(epoch):
             res = core.train_step(batch)
@@ -122,6 +130,8 @@ def main():
                 hits.update(res.metrics)
             if chains is not None and rank == 0:
                 chains.update(res.metrics)
+            if confs is not None and rank == 0:
+                confs.update(res.metrics)
             if res.stepped and rank == 0 and core.global_step % 10 == 0:
                 torch.cuda.synchronize()
                 acc = float(torch.stack(res.metrics["acces"]).mean())
@@ -140,6 +150,16 @@ def main():
                         rates = " ".join(f"{sm[f'chain_top{k}_acc_{i}']:.3f}" for i in range(args.ttt_length))
                         print(f"  top-{k} chains alive per depth: {rates}   chain_acc_len_top{k} {sm[f'chain_acc_len_top{k}']:.3f}", flush=True)
                     chains = ChainAccumulator(chain_ks)
+                if confs is not None:
+                    sm = confs.summary()
+                    if args.conf_bins:
+                        print("  calibration per depth (ece / mean confidence / top-1 rate): "
+                              + " ".join(f"{sm[f'conf_ece_{i}']:.3f}/{sm[f'conf_mean_{i}']:.3f}/{sm[f'conf_acc_{i}']:.3f}" for i in range(args.ttt_length)), flush=True)
+                    for t in conf_tau:
+                        nm = ConfidenceAccumulator.tau_name(t)
+                        print(f"  gated at conf >= {nm}: accepted {sm[f'gated_acc_len_tau{nm}']:.3f} of {sm[f'gated_draft_len_tau{nm}']:.3f} drafted per chain "
+                              f"({sm[f'gated_acc_per_draft_tau{nm}']:.3f})", flush=True)
+                    confs = ConfidenceAccumulator(args.conf_bins, conf_tau)
     if rank == 0:
         state = backend.state_dict()
         torch.save(strategy.checkpoint_state_filter(state["model"]), args.output)   # reference draft checkpoint keys

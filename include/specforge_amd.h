@@ -181,6 +181,32 @@ int sf_topk_rank(const void* logits, int dtype, long ld, int rows, int V, int S,
 int sf_chain_step(int rows, int S, int Spad, int off, long ntok, const int* loss_mask_pad, const long long* row_map,
                   const float* row_correct, const float* row_hit, int J, int* chain_depth, int* chain_len, float* row_out, void* stream);
 
+/* ---- draft confidence per row, calibration bins and confidence-gated chains (additive to ABI 6) ------------------------------
+ * sf_row_conf: conf = max softmax(z) = 1 / sum_j exp(z_j - max z) of every row with a loss mask, in fp32, at temperature 1 of the logits
+ * as stored.  logits / dtype / ld / V and the addressing (S, Spad, off, row_map) as sf_topk_rank: row r is token row
+ * rt = row_map ? row_map[r] : r = b*S+s and reads loss_mask_pad at b*Spad+s+off.  The output is indexed by TOKEN row: conf_tok fp32
+ * [ntok], ntok = B*S; conf_tok[rt] = -1.f for a row without a loss mask (it reads no logits).  A row_map entry outside [0, ntok) writes
+ * nothing, token rows not listed are not written.  Streaming, one workgroup per row, every logit read once and none written; the
+ * difference z_j - max is formed before any scaling; fixed reduction order, no atomics: bitwise repeatable.  rows == 0 launches nothing. */
+int sf_row_conf(const void* logits, int dtype, long ld, int rows, int V, int S, int Spad, int off, const int* loss_mask_pad,
+                const long long* row_map, long ntok, float* conf_tok, void* stream);
+
+/* sf_conf_fold: one TTT step's per-row calibration and gating values, after the step's fused CE.  With lm = loss mask != 0,
+ * c = conf_tok[rt], hit = row_correct[r] != 0 (the fused CE's), scored = lm && c >= 0, bin = min(NB-1, (int)(c * (float)NB)) (one fp32
+ * multiply, then truncation):
+ *     row_bins  fp32 [3*NB, rows]: [b][r] = scored && bin == b, [NB+b][r] = that && hit, [2*NB+b][r] = that ? c : 0
+ *     row_gate  fp32 [J, rows]:    [j][r] = scored && hit && c >= tau[j]       -- the row_hit operand of the gating fold's sf_chain_step
+ *     row_draft fp32 [J, rows]:    [j][r] = lm && gate_depth[rt] == off && gate_len[1+j][rt] == off && c >= tau[j]
+ * tau: a HOST array of J <= 8 thresholds in [0, 1], read during the call; NB <= 32.  gate_depth int32 [ntok] and gate_len int32
+ * [1+J, ntok] are the state arrays of a sf_chain_step fold whose channel 0 is row_correct and whose channels 1..J are row_gate; they are
+ * READ here, before that step's sf_chain_step call advances them: row_draft marks the rows whose gated chain accepted every shallower
+ * depth and proposes a token at this one.  0/1 (and c) laid out so that sf_reduce_sum(row_*, rows, channels, out, 1.0) gives the
+ * step's counts.  NB == 0 or J == 0 switch the corresponding outputs off (their pointers may be NULL), not both.  A row_map entry
+ * outside [0, ntok) writes zeros.  Plain loads and stores: bitwise repeatable.  rows == 0 launches nothing. */
+int sf_conf_fold(int rows, int S, int Spad, int off, long ntok, const int* loss_mask_pad, const long long* row_map,
+                 const float* conf_tok, const float* row_correct, int NB, int J, const float* tau, const int* gate_depth,
+                 const int* gate_len, float* row_bins, float* row_gate, float* row_draft, void* stream);
+
 /* ---- teacher soft targets from target logits ---------------------------------------------
  * replaces specforge/algorithms/eagle3/model.py:487-501 (_compute_target_p): argmax id
  * (lowest index on ties), position_mask = t2d[id]*loss_mask, target_p = softmax over the

@@ -35,6 +35,8 @@ _SIGS = {
     "sf_eagle3_metrics": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, P]),
     "sf_topk_rank": (c_int, [P, c_int, c_long, c_int, c_int, c_int, c_int, c_int, P, P, P, c_int, P, c_int, P, P, P, P]),
     "sf_chain_step": (c_int, [c_int, c_int, c_int, c_int, c_long, P, P, P, P, c_int, P, P, P, P]),
+    "sf_row_conf": (c_int, [P, c_int, c_long, c_int, c_int, c_int, c_int, c_int, P, P, c_long, P, P]),
+    "sf_conf_fold": (c_int, [c_int, c_int, c_int, c_int, c_long, P, P, P, P, c_int, c_int, P, P, P, P, P, P, P]),
     "sf_teacher_reduce": (c_int, [P, c_int, c_long, c_int, c_int, c_int, P, P, P, c_int, c_int, P, P, P, P, P, P]),
     "sf_gemm_nt_teacher": (c_int, [P, c_long, P, c_long, c_int, c_int, c_int, c_int, P, c_long, P, c_long, P, P, P]),
     "sf_teacher_reduce_perm": (c_int, [P, c_int, c_long, c_int, c_int, c_int, c_int, P, P, P, c_int, c_long, P, c_int, c_int, P, P, P, P,

@@ -10,6 +10,7 @@ gradient buffer the parameters' ``.grad`` alias.
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass, field
 from typing import Any, Dict, Optional, Tuple
 
@@ -106,7 +107,7 @@ class OnlineEagle3Model(nn.Module):
     def __init__(self, draft_model: LlamaForCausalLMEagle3, length: int = 7, attention_backend: str = "hip",
                  lk_loss_type: Optional[str] = None, kl_scale: float = 1.0, kl_decay: float = 1.0,
                  ploss_decay: float = 0.8, sp_group=None, sp_ulysses_group=None, sp_ring_group=None, mrope_analytic: bool = False, topk=(),
-                 chain: bool = False):
+                 chain: bool = False, conf_bins: int = 0, conf_thresholds=()):
         """``attention_backend="usp"``: Ulysses sequence parallelism over ``sp_group`` (set here, or later by
         ``HipDPTrainingBackend.prepare_model`` / the strategy, before the first forward); every other value runs the one-rank
         attention.  ``sp_ring_group`` (with ``sp_ulysses_group``, None for a pure ring): ring x Ulysses over the same SP group
@@ -116,7 +117,11 @@ class OnlineEagle3Model(nn.Module):
         the draft's top k (denominators: ``acc_denoms``).  The return tuple of ``forward`` is the reference's seven lists either way.
         ``chain``: ``Eagle3Engine.chain`` -- the joint accepted length of the draft chains; after every forward ``last_chain`` =
         (denoms, corrects): per TTT step the count of rows with a loss mask at every depth so far, and the [1 + len(topk)] counts of
-        those that hit at every depth so far (channel 0 top-1, then ``topk``); None when off."""
+        those that hit at every depth so far (channel 0 top-1, then ``topk``); None when off.
+        ``conf_bins`` / ``conf_thresholds``: ``Eagle3Engine.conf_bins`` / ``.conf_thresholds`` -- the draft's top-1 softmax probability
+        per row; after every forward ``last_conf`` = (bins, denoms, gate): per TTT step the [3, conf_bins] reliability bins (rows, top-1
+        hits, confidence sum), the count of rows with a loss mask at every depth so far, and the [len(conf_thresholds), 2] (drafted,
+        accepted) counts of the confidence-gated chains; None when both are unset."""
         super().__init__()
         if lk_loss_type not in (None, "alpha", "lambda"):
             raise ValueError(f"Unknown lk loss type: {lk_loss_type}")  # core/lk_loss.py:99
@@ -134,6 +139,8 @@ class OnlineEagle3Model(nn.Module):
         self.last_topk = None
         self.chain = bool(chain)
         self.last_chain = None
+        self.conf_bins, self.conf_thresholds = Eagle3Engine._check_conf(conf_bins, conf_thresholds)
+        self.last_conf = None
         self._engine: Optional[Eagle3Engine] = None
         dev = next(draft_model.parameters()).device
         self._anchor = nn.Parameter(torch.zeros((), device=dev), requires_grad=True)
@@ -153,7 +160,8 @@ class OnlineEagle3Model(nn.Module):
             self._engine = Eagle3Engine(self.draft_model, ttt_length=self.length, ploss_decay=self.ploss_decay,
                                         lk_loss_type=self.lk_loss_type, kl_scale=self.kl_scale, kl_decay=self.kl_decay,
                                         sp_group=sp_group, sp_ulysses_group=uly_group, sp_ring_group=ring_group,
-                                        mrope_analytic=self.mrope_analytic, topk=self.topk, chain=self.chain)
+                                        mrope_analytic=self.mrope_analytic, topk=self.topk, chain=self.chain,
+                                        conf_bins=self.conf_bins, conf_thresholds=self.conf_thresholds)
             object.__setattr__(self.draft_model, "_hip_engine", self._engine)   # found by BF16Optimizer(draft_model)
         return self._engine
 
@@ -184,6 +192,8 @@ class OnlineEagle3Model(nn.Module):
             self.engine.topk = self.topk
         if self.engine.chain != bool(self.chain):
             self.engine.chain = self.chain
+        if (self.engine.conf_bins, self.engine.conf_thresholds) != Eagle3Engine._check_conf(self.conf_bins, self.conf_thresholds):
+            self.engine._set_conf(self.conf_bins, self.conf_thresholds)
         if position_span is None and position_ids is not None and not position_ids.is_cuda and position_ids.numel():
             position_span = (int(position_ids.min()), int(position_ids.max()))
         to = lambda t: None if t is None else t.to(dev)
@@ -198,6 +208,7 @@ class OnlineEagle3Model(nn.Module):
         self.last_artifacts = dict(target_token_ids=out["target_token_ids"], position_mask=out["position_mask"])
         self.last_topk = out.get("topk_corrects")
         self.last_chain = (out["chain_denoms"], out["chain_corrects"]) if "chain_denoms" in out else None
+        self.last_conf = (out["conf_bins"], out["conf_denoms"], out["conf_gate"]) if "conf_bins" in out else None
         return (list(plosses.unbind(0)), out["acceptance_rates"], out["acces"], out["acc_corrects"], out["acc_denoms"],
                 out["metric_losses"], out["metric_loss_denoms"])
 
@@ -342,6 +353,14 @@ class Eagle3TrainStrategy:
             metrics["chain_denoms"] = [x.detach() for x in ch[0]]
             for h, kth in enumerate((1,) + tuple(self.eagle3_model.topk)):
                 metrics.setdefault(f"chain_top{kth}_corrects", [step[h].detach() for step in ch[1]])
+        cf = self.eagle3_model.last_conf
+        if cf is not None:      # lists over the T steps of [NB] / 0-dim / [J] counts (the reference's trainer and evaluator skip them)
+            metrics["conf_bin_counts"] = [step[0].detach() for step in cf[0]]
+            metrics["conf_bin_corrects"] = [step[1].detach() for step in cf[0]]
+            metrics["conf_bin_sums"] = [step[2].detach() for step in cf[0]]
+            metrics["conf_denoms"] = [x.detach() for x in cf[1]]
+            metrics["conf_gate_drafted"] = [step[:, 0].detach() for step in cf[2]]
+            metrics["conf_gate_accepted"] = [step[:, 1].detach() for step in cf[2]]
         return StepOutput(loss=loss, metrics=metrics)
 
     def checkpoint_state_filter(self, state_dict: Dict[str, Any]) -> Dict[str, Any]:
@@ -435,6 +454,63 @@ class ChainAccumulator:
             for i, a in enumerate(rates[j]):
                 out[f"chain_top{k}_acc_{i}"] = float(a)
             out[f"chain_acc_len_top{k}"] = float(sum(rates[j]))
+        return out
+
+
+class ConfidenceAccumulator:
+    """Calibration of the draft's confidence and the length of confidence-gated chains over many batches
+    (``OnlineEagle3Model(conf_bins=, conf_thresholds=)``): float64 sums of the ``conf_*`` metrics per TTT depth, on the metrics' device,
+    every ratio taken after the sums, 0 where a denominator is 0.
+
+    Confidence is the draft's top-1 probability: the softmax at temperature 1 of the logits as stored.  ``summary()`` per depth i, over the
+    rows scored at that depth (a loss mask; like ``acces``, not restricted to chains still alive): ``conf_mean_i``, ``conf_acc_i`` (the
+    top-1 hit rate), ``conf_ece_i`` = sum_b n_b / n * |hits_b / n_b - sum_b / n_b| (the expected calibration error over the ``bins``
+    equal-width bins) and ``conf_reliability_i``, the table: per occupied or empty bin a tuple (count, accuracy, mean confidence).
+
+    Per threshold tau: ``gated_acc_len_tau{tau}`` = sum_k accepted_k / denoms_0 and ``gated_draft_len_tau{tau}`` = sum_k drafted_k /
+    denoms_0 -- accepted and drafted tokens per chain, over the rows scored at depth 0 -- and ``gated_acc_per_draft_tau{tau}``, their
+    ratio.  Teacher-forced, as ``chain_acc_len_top1``.  ACCEPTED is exact for a greedy chain that stops drafting at the first depth
+    whose confidence is under tau.  DRAFTED counts the tokens such a chain proposes up to and including its first rejected one; what a
+    drafter proposes AFTER its first wrong token is not observable teacher-forced (its inputs would be its own tokens), so the draft
+    cost is a lower bound.  A chain censored by a position without a loss mask stops counting on both sides."""
+
+    def __init__(self, bins, thresholds):
+        self.bins, self.thresholds = Eagle3Engine._check_conf(bins, thresholds)
+        self.sums: Optional[Dict[str, torch.Tensor]] = None     # key -> float64 [T, ...]
+
+    _KEYS = ("conf_bin_counts", "conf_bin_corrects", "conf_bin_sums", "conf_denoms", "conf_gate_drafted", "conf_gate_accepted")
+
+    def update(self, metrics: Dict[str, Any]) -> None:
+        """``metrics`` = ``StepOutput.metrics`` of a strategy whose model has ``conf_bins`` / ``conf_thresholds`` set"""
+        new = {k: torch.stack([torch.as_tensor(v).detach().double() for v in metrics[k]]) for k in self._KEYS}
+        if self.sums is None:
+            self.sums = {k: torch.zeros_like(v) for k, v in new.items()}
+        for k, v in new.items():
+            self.sums[k] += v.to(self.sums[k].device)
+
+    @staticmethod
+    def tau_name(tau: float) -> str:
+        return f"{tau:g}"
+
+    def summary(self) -> Dict[str, Any]:
+        if self.sums is None:
+            return {}
+        sm = {k: v.cpu().tolist() for k, v in self.sums.items()}       # (one read-back; math.fsum: correctly rounded, so order-free)
+        cnt, hit, cs, den = sm["conf_bin_counts"], sm["conf_bin_corrects"], sm["conf_bin_sums"], sm["conf_denoms"]
+        out: Dict[str, Any] = {}
+        for i in range(len(cnt) if self.bins else 0):
+            n = math.fsum(cnt[i])
+            out[f"conf_ece_{i}"] = math.fsum(c * abs(h / c - z / c) for c, h, z in zip(cnt[i], hit[i], cs[i]) if c > 0) / n if n > 0 else 0.0
+            out[f"conf_mean_{i}"] = math.fsum(cs[i]) / n if n > 0 else 0.0
+            out[f"conf_acc_{i}"] = math.fsum(hit[i]) / n if n > 0 else 0.0
+            out[f"conf_reliability_{i}"] = [(c, h / c if c > 0 else 0.0, z / c if c > 0 else 0.0) for c, h, z in zip(cnt[i], hit[i], cs[i])]
+        d0 = float(den[0])
+        for j, tau in enumerate(self.thresholds):
+            acc, dr = math.fsum(row[j] for row in sm["conf_gate_accepted"]), math.fsum(row[j] for row in sm["conf_gate_drafted"])
+            name = self.tau_name(tau)
+            out[f"gated_acc_len_tau{name}"] = acc / d0 if d0 > 0 else 0.0
+            out[f"gated_draft_len_tau{name}"] = dr / d0 if d0 > 0 else 0.0
+            out[f"gated_acc_per_draft_tau{name}"] = acc / dr if dr > 0 else 0.0
         return out
 
 

@@ -252,6 +252,56 @@ def chain_step(*, rows: int, S: int, Spad: int, off: int, loss_mask_pad, row_cor
                                _p(chain_depth), _p(chain_len), _p(row_out), _stream()), "sf_chain_step")
 
 
+CONF_MAX_BINS = 32     # reliability bins per sf_conf_fold launch
+CONF_MAX_TAU = 8       # gating thresholds per sf_conf_fold launch
+
+
+def row_conf(logits: torch.Tensor, *, S: int, Spad: int, off: int, loss_mask_pad, conf_tok, row_map=None):
+    """The draft's top-1 softmax probability of every row with a loss mask, ``conf_tok[rt] = 1 / sum_j exp(z_j - max z)`` in fp32
+    (include/specforge_amd.h, sf_row_conf): ``conf_tok`` fp32 [ntok] is indexed by TOKEN row (``rt = row_map[r]``, or r), -1 where the
+    row has no loss mask; token rows not listed keep their value.  Addressing (S, Spad, off, row_map) as ``topk_rank``.  Reads only."""
+    L = _lib.lib()
+    rows, V = logits.shape
+    ntok = conf_tok.numel()
+    assert loss_mask_pad.dtype == torch.int32 and loss_mask_pad.is_contiguous() and S > 0 and loss_mask_pad.numel() >= ntok // S * Spad
+    assert row_map is None or (row_map.dtype == torch.int64 and row_map.numel() >= rows and row_map.is_contiguous())
+    assert row_map is not None or rows <= ntok
+    assert conf_tok.dtype == torch.float32 and conf_tok.is_contiguous()
+    _lib.check(L.sf_row_conf(_p(logits), _dt(logits), _rowmajor(logits), rows, V, S, Spad, off, _p(loss_mask_pad), _p(row_map), ntok,
+                             _p(conf_tok), _stream()), "sf_row_conf")
+
+
+def conf_fold(*, rows: int, S: int, Spad: int, off: int, loss_mask_pad, conf_tok, row_correct, bins: int = 0, tau: Sequence[float] = (),
+              gate_depth=None, gate_len=None, row_bins=None, row_gate=None, row_draft=None, row_map=None):
+    """One TTT step's calibration and gating rows (include/specforge_amd.h, sf_conf_fold), after the step's fused CE: ``row_bins``
+    fp32 [3 * bins, rows] (in bin, in bin and hit, conf in bin), ``row_gate`` fp32 [J, rows] (hit with conf >= tau[j]: the ``row_hit``
+    of the gating fold's ``chain_step``) and ``row_draft`` fp32 [J, rows] (the gated chain is still open at this depth and proposes a
+    token).  ``gate_depth`` int32 [ntok] / ``gate_len`` int32 [1 + J, ntok]: the state of that fold, read BEFORE its ``chain_step`` of
+    this step.  Addressing (S, Spad, off, row_map) as ``topk_rank``; ``conf_tok`` is indexed by token row."""
+    L = _lib.lib()
+    rows, NB = int(rows), int(bins)
+    if rows >= CHAIN_MAX_ROWS:
+        raise ValueError(f"conf_fold: {rows} rows; the fp32 counts are exact below {CHAIN_MAX_ROWS}")
+    tau = [float(t) for t in tau]
+    J = len(tau)
+    ntok = conf_tok.numel()
+    assert conf_tok.dtype == torch.float32 and conf_tok.is_contiguous() and ntok > 0
+    assert loss_mask_pad.dtype == torch.int32 and loss_mask_pad.is_contiguous() and S > 0 and loss_mask_pad.numel() >= ntok // S * Spad
+    assert row_map is None or (row_map.dtype == torch.int64 and row_map.numel() >= rows and row_map.is_contiguous())
+    assert row_map is not None or rows <= ntok
+    assert row_correct.dtype == torch.float32 and row_correct.numel() >= rows and row_correct.is_contiguous()
+    assert NB == 0 or (row_bins is not None and row_bins.dtype == torch.float32 and row_bins.numel() >= 3 * NB * rows and row_bins.is_contiguous())
+    if J:
+        assert gate_depth.dtype == torch.int32 and gate_len.dtype == torch.int32 and gate_depth.is_contiguous() and gate_len.is_contiguous()
+        assert gate_depth.numel() == ntok and gate_len.numel() == (1 + J) * ntok
+        for o in (row_gate, row_draft):
+            assert o is not None and o.dtype == torch.float32 and o.numel() >= J * rows and o.is_contiguous()
+    arr = (ctypes.c_float * max(1, J))(*tau)
+    _lib.check(L.sf_conf_fold(rows, S, Spad, off, ntok, _p(loss_mask_pad), _p(row_map), _p(conf_tok), _p(row_correct), NB, J, arr,
+                              _p(gate_depth) if J else None, _p(gate_len) if J else None, _p(row_bins) if NB else None,
+                              _p(row_gate) if J else None, _p(row_draft) if J else None, _stream()), "sf_conf_fold")
+
+
 def teacher_reduce(z: torch.Tensor, *, Vd: int, d2t, t2d_u8, loss_mask_pad, S: int, Spad: int, target_p_pad,
                    pod_scale_pad, tsum_pad, ids_pad, pos_mask_pad, row0: int = 0):
     """rows of z are tokens row0 .. row0+rows (row index b*S+s)."""

@@ -132,7 +132,8 @@ def _training_model_factory():
         check_training_topology(t, draft_config, mode=getattr(config, "mode", None))
         model = OnlineEagle3Model(draft_model=draft_model, length=t.ttt_length, attention_backend=t.attention_backend,
                                   lk_loss_type=t.lk_loss_type, kl_scale=t.kl_scale, kl_decay=t.kl_decay, topk=_options.get("topk", ()),
-                                  chain=_options.get("chain", False))
+                                  chain=_options.get("chain", False), conf_bins=_options.get("conf_bins", 0),
+                                  conf_thresholds=_options.get("conf_thresholds", ()))
         model = model.to(device=mp._device(), dtype=mp._torch_dtype(config))
         target_head = None
         if config.mode == "offline" or (config.deployment.mode == "disaggregated" and t.role == "consumer"):
@@ -387,14 +388,22 @@ class _HipBackendForTrainer(HipDPTrainingBackend):
 _options: dict = {}      # settings of the HIP path that the reference's strict run schema has no key for (install(...) sets them)
 
 
-def install(override: bool = False, topk=None, chain=None) -> None:
+def install(override: bool = False, topk=None, chain=None, conf_bins=None, conf_thresholds=None) -> None:
     """Rebind the constructors the reference hard-codes (module docstring, b3 / f1): the trainer's backend, its feature
     loader and the configured optimizer factory's class; with ``override=True`` also the draft registry entry ``LlamaForCausalLMEagle3``.
     Idempotent; ``uninstall()`` restores everything (e.g. before ``export --to sglang`` materialises the reference's
     own class from the same draft config).  ``topk`` (e.g. ``(1, 2, 4, 8)``; None leaves the setting as it is): the models the
     algorithm's factory builds from now on report top-k hit counts (``OnlineEagle3Model(topk=...)``, ``top{k}_corrects`` in
     ``StepOutput.metrics``); ``chain`` (True / False; None leaves it): they also report the joint chain counts
-    (``OnlineEagle3Model(chain=...)``, ``chain_denoms`` and ``chain_top{k}_corrects``); ``uninstall()`` clears both."""
+    (``OnlineEagle3Model(chain=...)``, ``chain_denoms`` and ``chain_top{k}_corrects``); ``conf_bins`` (e.g. 10) / ``conf_thresholds`` (e.g. ``(0.3, 0.5, 0.7)``; None leaves
+    each): the draft's confidence -- reliability bins per TTT step and the drafted / accepted counts of confidence-gated chains
+    (``OnlineEagle3Model(conf_bins=, conf_thresholds=)``, the ``conf_*`` keys); ``uninstall()`` clears them all."""
+    if conf_bins is not None or conf_thresholds is not None:
+        from .engine import Eagle3Engine
+
+        nb, tau = Eagle3Engine._check_conf(_options.get("conf_bins", 0) if conf_bins is None else conf_bins,
+                                           _options.get("conf_thresholds", ()) if conf_thresholds is None else conf_thresholds)
+        _options["conf_bins"], _options["conf_thresholds"] = nb, tau
     if chain is not None:
         _options["chain"] = bool(chain)
     if topk is not None:
@@ -469,7 +478,8 @@ def main(argv=None, *, worker_prefix=None) -> int:
     (default: ``python -m specforge_amd.reference_plugin``; the test suite's harness entry passes itself).  Single-node launches
     rendezvous on 127.0.0.1 (``--local-addr``: container host names need not resolve).  ``--topk 1,2,4,8`` (before or after ``train``):
     top-k hit counts in the step metrics (``install(topk=...)``; the run YAML is a strict schema and has no key for it) -- handed on to
-    spawned workers on their command line.  ``--chain`` beside it: the joint chain counts (``install(chain=True)``)."""
+    spawned workers on their command line.  ``--chain`` beside it: the joint chain counts (``install(chain=True)``).
+    ``--conf-bins N`` / ``--conf-thresholds a,b,c`` likewise: the draft-confidence metrics (``install(conf_bins=, conf_thresholds=)``)."""
     import argparse
     import os
     import sys
@@ -477,14 +487,19 @@ def main(argv=None, *, worker_prefix=None) -> int:
     from specforge import cli
 
     argv = list(sys.argv[1:] if argv is None else argv)
-    topk_csv, chain_flag = None, False
-    while argv and argv[0] in ("--topk", "--chain"):    # (in front of the sub-command: where a spawned worker's prefix carries them)
+    topk_csv, chain_flag, conf_bins_arg, conf_tau_csv = None, False, None, None
+    while argv and argv[0] in ("--topk", "--chain", "--conf-bins", "--conf-thresholds"):
+        # (in front of the sub-command: where a spawned worker's prefix carries them)
         if argv[0] == "--chain":
             chain_flag, argv = True, argv[1:]
-        elif len(argv) >= 2:
-            topk_csv, argv = argv[1], argv[2:]
-        else:
+        elif len(argv) < 2:
             break
+        elif argv[0] == "--topk":
+            topk_csv, argv = argv[1], argv[2:]
+        elif argv[0] == "--conf-bins":
+            conf_bins_arg, argv = int(argv[1]), argv[2:]
+        else:
+            conf_tau_csv, argv = argv[1], argv[2:]
     if not argv or argv[0] != "train":
         return cli.main(argv)
     ap = argparse.ArgumentParser(prog="python -m specforge_amd.reference_plugin train")
@@ -495,15 +510,19 @@ def main(argv=None, *, worker_prefix=None) -> int:
     ap.add_argument("--topk", default=topk_csv, help="comma-separated k, e.g. 1,2,4,8: top-k hit counts in the step metrics")
     ap.add_argument("--chain", action="store_true", default=chain_flag,
                     help="joint chain counts (chain_denoms, chain_top{k}_corrects) in the step metrics")
+    ap.add_argument("--conf-bins", type=int, default=conf_bins_arg, help="reliability bins of the draft's confidence per TTT step (at most 32)")
+    ap.add_argument("--conf-thresholds", default=conf_tau_csv,
+                    help="comma-separated confidence thresholds in [0, 1], e.g. 0.3,0.5,0.7: drafted / accepted counts of gated chains")
     ap.add_argument("overrides", nargs="*")
     args = ap.parse_args(argv[1:])
     topk = tuple(int(k) for k in args.topk.split(",") if k.strip()) if args.topk else None
+    conf_tau = tuple(float(t) for t in args.conf_thresholds.split(",") if t.strip()) if args.conf_thresholds else None
 
     from specforge.application import bind_run, resolve_run
     from specforge.config import load_config
     from specforge.launch_plan import build_launch_plan, run_commands
 
-    install(override=True, topk=topk, chain=True if args.chain else None)
+    install(override=True, topk=topk, chain=True if args.chain else None, conf_bins=args.conf_bins, conf_thresholds=conf_tau)
     cfg = load_config(args.config, args.overrides)
     check_training_topology(cfg.training, _draft_config_dict(cfg), mode=cfg.mode)    # before any process group or engine exists
     resolved = resolve_run(cfg, registry=registry(override=True))
@@ -512,6 +531,10 @@ def main(argv=None, *, worker_prefix=None) -> int:
         me = me + ("--topk", ",".join(str(k) for k in topk))
     if args.chain:
         me = me + ("--chain",)
+    if args.conf_bins:
+        me = me + ("--conf-bins", str(args.conf_bins))
+    if conf_tau:
+        me = me + ("--conf-thresholds", ",".join(repr(t) for t in conf_tau))
     plan = build_launch_plan(resolved.config, algorithm=resolved.algorithm, config_path=args.config, overrides=args.overrides,
                              requested_role=args.role, node_rank=args.node_rank, worker_prefix=me,
                              torchrun_prefix=(sys.executable, "-m", "torch.distributed.run", "--no-python", "--local-addr", "127.0.0.1"))
